@@ -6,8 +6,14 @@ A step = one render of the whole image of randSpheres (main.go:227-289, seeded),
 row-interleaved over the N ranks (one process per GPU), plus the RCCL gather of the shards
 to rank 0 when N > 1.  Scene tables are uploaded to HBM before timing.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--spp S]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--spp S] [--dump-outputs DIR] [--full]
   --spp 2000 is configs[2] (1920x1080x2000, meant for 8 GPUs).
+  A plain run does what the headline figure needs: the scene upload, one untimed counting render (the rays of a
+  step), the warmup, the K timed steps with the library's error check after them, the result line.
+  --dump-outputs DIR writes the frame the last timed step produced to DIR/image.npy (float32 [rows, width, 3]:
+  what a caller of the timed path receives; same arguments, same inputs, so two builds compare pixel for pixel).
+  --full adds everything else: the framebuffer hashes and the untimed verify render, the roofline from the
+  committed PMC summaries, the CPU oracle timed on the host, and (N > 1) rank 0's in-process leg.
   N > 1 either under torch.distributed.run (RANK/WORLD_SIZE in the environment), or plain
   `python bench.py --gpus N`: the process then starts N rank processes itself (before any
   GPU call) and exits with their status.
@@ -48,6 +54,12 @@ def parse():
     ap.add_argument("--scene", default="random_spheres")
     ap.add_argument("--scene-seed", type=int, default=1)
     ap.add_argument("--seed", type=int, default=2024)
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the last timed step's frame to DIR/image.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also: framebuffer hashes + the untimed verify render, the roofline from the PMC summaries, "
+                         "the CPU baseline, (N > 1) the in-process leg; --no-cpu / --no-hash / --no-verify / "
+                         "--no-in-process then leave one of them out")
     ap.add_argument("--cpu-target-s", type=float, default=15.0, help="CPU baseline budget (seconds)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: the host's CPU share per GPU")
     ap.add_argument("--no-cpu", action="store_true")
@@ -319,6 +331,22 @@ def walk_desc(st, skips, near_skips, cam) -> str:
     return f"rebuilt tree, camera octant {lay}, " + col(skips)
 
 
+def dump_outputs(path: str, img) -> None:
+    """--dump-outputs: the frame of the last timed step as DIR/image.npy, float32 [rows, width, 3] (24.9 MB at
+    1920x1080).  A frame over 60 MB (3840x2160 is 99.5 MB) is written as a fixed, seeded sample of 2 M of its
+    pixels instead: image.npy [n, 3] (24 MB) and image_index.npy, their flat pixel indices as float64 (16 MB)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    a = np.ascontiguousarray(img if isinstance(img, np.ndarray) else img.detach().cpu().numpy(), dtype=np.float32)
+    if a.nbytes > 60 * 1000 * 1000:
+        px = a.reshape(-1, 3)
+        idx = np.sort(np.random.default_rng(20240607).choice(px.shape[0], size=2_000_000, replace=False))
+        np.save(os.path.join(path, "image_index.npy"), idx.astype(np.float64))
+        a = np.ascontiguousarray(px[idx])
+    np.save(os.path.join(path, "image.npy"), a)
+
+
 def framebuffer_hash(img) -> str:
     import numpy as np
 
@@ -428,11 +456,15 @@ def main():
     # (rtx_device_check reads the error word no render clears: one check covers all K).
     rtx.device_check(torch.cuda.current_device())
     # the frame the last timed step produced (rank 0: the gathered image), hashed before anything renders again
-    timed_hash = framebuffer_hash(timed_img) if rank == 0 and not args.no_hash else None
+    hashed = args.full and not args.no_hash
+    verify = args.full and not args.no_verify
+    timed_hash = framebuffer_hash(timed_img) if rank == 0 and hashed else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed_img)
     kms = [e0.elapsed_time(e1) for e0, e1, _ in evs]
     gms = [e1.elapsed_time(e2) for _, e1, e2 in evs]
     img = timed_img
-    if not args.no_verify:
+    if verify:
         img = step([], [])  # (untimed: the frame once more, with the library's stats and error check)
     t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if shared else "cuda")
     if world > 1:
@@ -496,28 +528,29 @@ def main():
             "walk_layout": walk_desc(st, skips, near_skips, cam),
             "prim_tests_per_segment": round(tot["prim_tests"] / tot["segments"], 3),
             "schedule": schedule(st),
-            "roofline": roofline(st, my_rows * W, avg_kernel_s, profile_workload, args.traffic, args.valu),
         }
-        if sworld > 1:
+        if args.full:
+            out["roofline"] = roofline(st, my_rows * W, avg_kernel_s, profile_workload, args.traffic, args.valu)
+        if args.full and sworld > 1:
             out["roofline"]["scope"] = (f"rank {srank}'s kernel on its own rows ({my_rows} of {H}), against the PMC "
                                         f"profile of that shard rendered alone (bench.py --shard {srank}/{sworld})")
         if world > 1:  # rank 0's wall time in the gather (incl. waiting for the slowest rank)
             out["gather_ms_avg"] = round(sum(gms) / len(gms), 3)
             out["kernel_ms_per_rank"] = {"min": round(min(rank_kms), 3), "max": round(max(rank_kms), 3),
                                          "all": [round(x, 3) for x in rank_kms]}
-        if not args.no_hash:
+        if hashed:
             out["framebuffer_sha256_16"] = framebuffer_hash(img)  # bitwise-comparable across N
             # the last timed step's own frame: equal to the checked frame, or the timed region rendered something else
             out["timed_frames_hash"] = timed_hash
             out["timed_frames_checked"] = (f"rtx_device_check after the {args.steps} timed renders: no watchdog stop, "
                                            "no partial-wave claim; the last timed frame's hash "
-                                           + ("equals the verify render's" if not args.no_verify else
+                                           + ("equals the verify render's" if verify else
                                               "(no verify render: --no-verify)"))
-            if not args.no_verify and timed_hash != out["framebuffer_sha256_16"]:
+            if verify and timed_hash != out["framebuffer_sha256_16"]:
                 print(json.dumps(out), flush=True)
                 raise SystemExit(f"the last timed frame ({timed_hash}) differs from the verify render "
                                  f"({out['framebuffer_sha256_16']})")
-        if world == 1 and not args.no_cpu and not args.shard:
+        if args.full and world == 1 and not args.no_cpu and not args.shard:
             out["cpu_baseline"] = cpu_baseline(scene, cam, args.seed, args.cpu_target_s, args.cpu_threads)
             # the same rows on every CPU the process may use: the reference's own concurrency (runtime.NumCPU()
             # workers, camera.go:167); the one-GPU share above stays the headline baseline
@@ -529,7 +562,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world > 1 and not shared and not args.no_in_process:
+        if args.full and world > 1 and not shared and not args.no_in_process:
             out["in_process"] = in_process_leg(args, world)
         print(json.dumps(out), flush=True)
 
@@ -581,6 +614,8 @@ def main_in_process(args):
         kms.append(s.kernel_ms)
         gms.append(s.gather_ms)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, buf)
     out = {
         "metric": f"Mray/s on {W}x{H}x{S}spp {args.scene}, one process driving {n} GPUs (rtx_render)",
         "value": round(st.segments * args.steps / elapsed / 1e6, 3),

@@ -22,7 +22,7 @@ for args in "${WS[@]}"; do
     for var in "${VS[@]}"; do
       v=$((v+1))
       f="$OUT/w$w.v$v.r$rep"
-      env $(echo "$var" | tr ';' ' ') timeout -k 10 ${LIMIT:-300} python bench.py --no-cpu --steps ${STEPS:-5} \
+      env $(echo "$var" | tr ';' ' ') timeout -k 10 ${LIMIT:-300} python bench.py --full --no-cpu --steps ${STEPS:-5} \
           --warmup 1 $args > "$f.json" 2> "$f.err" || { tail -5 "$f.err"; exit 1; }
       python -c "import json,sys; d=json.load(open(sys.argv[1])); s=d.get('schedule',{}); print(sys.argv[2], '|', sys.argv[3], '|', d['ms_per_step'], d['kernel_ms_avg'], d['framebuffer_sha256_16'], d['node_visits_per_segment'], d['prim_tests_per_segment'], d['walk_layout'][:60])" "$f.json" "$args" "$var"
     done

@@ -8,7 +8,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 R=${ROUND:-06}; OUT="$PWD/gpurun_out/${TAG:-configs$R}"; mkdir -p "$OUT"; export TMPDIR=/tmp
 run() {  # name, args...
   local n=$1; shift
-  timeout -k 10 400 python bench.py --steps 3 --warmup 1 --cpu-target-s 5 --valu profiles/valu_r$R.jsonl --traffic profiles/traffic_r$R.jsonl "$@" > "$OUT/$n.json" 2> "$OUT/$n.err" || return $?
+  timeout -k 10 400 python bench.py --full --steps 3 --warmup 1 --cpu-target-s 5 --valu profiles/valu_r$R.jsonl --traffic profiles/traffic_r$R.jsonl "$@" > "$OUT/$n.json" 2> "$OUT/$n.err" || return $?
   tail -1 "$OUT/$n.json" >> "$OUT/configs.jsonl"
   tail -1 "$OUT/$n.json" | cut -c1-220
 }

@@ -9,7 +9,7 @@ TAG=${TAG:-shards${ROUND:-06}}; OUT="$PWD/gpurun_out/$TAG"; mkdir -p "$OUT"; exp
 : > "$OUT/shards.jsonl"
 for N in 2 4 8; do
   for ((r = 0; r < N; r++)); do
-    timeout -k 10 200 python bench.py --shard $r/$N --no-cpu --steps 3 --warmup 1 > "$OUT/s${r}of$N.json" 2> "$OUT/s${r}of$N.err" || \
+    timeout -k 10 200 python bench.py --shard $r/$N --full --no-cpu --steps 3 --warmup 1 > "$OUT/s${r}of$N.json" 2> "$OUT/s${r}of$N.err" || \
         { tail -5 "$OUT/s${r}of$N.err"; exit 1; }
     python - "$OUT/s${r}of$N.json" $r $N >> "$OUT/shards.jsonl" << 'PY'
 import json, sys

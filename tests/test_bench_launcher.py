@@ -64,7 +64,7 @@ def test_rank_processes_render_the_same_image_on_one_gpu(n):
     processes on cuda:0, each renders its row-interleaved shard with the megakernel (8 x 8 tiles at N = 3,
     16 x 4 at N = 4, 32 x 2 at N = 8), and the shards are gathered (gloo, host copies: RCCL needs a GPU per
     rank) and de-interleaved on rank 0.  The framebuffer hash must equal the one-rank render's bit for bit."""
-    common = ["--width", "192", "--spp", "8", "--steps", "1", "--warmup", "0", "--no-cpu"]
+    common = ["--width", "192", "--spp", "8", "--steps", "1", "--warmup", "0", "--full", "--no-cpu"]
     one = _bench_line(["--gpus", "1"] + common)
     many = _bench_line(["--gpus", str(n), "--rehearse-one-gpu"] + common)
     assert many["n_gpus"] == n and many["config"]["world_size"] == n and many["config"]["backend"] == "gloo"
@@ -92,7 +92,7 @@ def test_in_process_leg_on_one_gpu(env, kind):
     after its ranks' steps.  On one GPU: RTX_SIM_BANDS=3 renders three bands on device 0 and assembles
     them as the gather does; RTX_FORCE_RCCL=1 runs the ncclGather as a 1-rank gather.  Same framebuffer as
     the one-rank bench, the gather timed."""
-    common = ["--width", "192", "--spp", "8", "--steps", "2", "--warmup", "1", "--no-cpu"]
+    common = ["--width", "192", "--spp", "8", "--steps", "2", "--warmup", "1", "--full", "--no-cpu"]
     one = _bench_line(["--gpus", "1"] + common)
     got = _bench_line_env(["--in-process", "--gpus", "1"] + common, env)
     assert got["gather_kind"] == kind and got["gather_ms_avg"] > 0
@@ -104,6 +104,30 @@ def test_in_process_leg_on_one_gpu(env, kind):
 def test_shard_run_renders_its_rows():
     """`bench.py --shard 1/3`: rank 1's rows of a 3-way run rendered alone (its PMC profile's workload):
     the metric says so, and the roofline looks up that shard's own profile."""
-    got = _bench_line(["--shard", "1/3", "--width", "192", "--spp", "8", "--steps", "1", "--warmup", "0", "--no-cpu"])
+    got = _bench_line(["--shard", "1/3", "--width", "192", "--spp", "8", "--steps", "1", "--warmup", "0", "--full",
+                       "--no-cpu"])
     assert got["metric"].startswith("shard 1/3")
     assert got["roofline"]["workload"].endswith("/rows1of3") and "rank 1's kernel" in got["roofline"]["scope"]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_timed_frame(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` prints the headline line alone (no hashes, no roofline, no
+    CPU baseline: those are `--full`'s), `--steps` sets the timed steps, and `--dump-outputs DIR` writes the last
+    timed step's frame as DIR/image.npy (float32): the bytes `--full` hashes as timed_frames_hash."""
+    common = ["--gpus", "1", "--width", "192", "--spp", "8", "--steps", "2", "--warmup", "1"]
+    plain = _bench_line(common + ["--dump-outputs", str(tmp_path / "dump")])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in plain, key
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    for key in ("cpu_baseline", "cpu_baseline_full_host", "roofline", "framebuffer_sha256_16", "timed_frames_hash"):
+        assert key not in plain, key
+    assert sorted(os.listdir(tmp_path / "dump")) == ["image.npy"]
+    img = np.load(tmp_path / "dump" / "image.npy")
+    assert img.dtype == np.float32 and img.shape == (108, 192, 3) and np.isfinite(img).all() and img.max() > 0
+    full = _bench_line(common + ["--full", "--no-cpu"])
+    assert full["timed_frames_hash"] == full["framebuffer_sha256_16"]
+    assert hashlib.sha256(img.tobytes()).hexdigest()[:16] == full["timed_frames_hash"]
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert plain[key] == full[key], key
+    assert "roofline" in full

@@ -116,7 +116,8 @@ def test_bench_fails_on_a_flagged_timed_step(built):
     """bench.py's timed renders are checked: a partial-wave claim in the 2nd of 3 timed steps (enqueued with no
     stats read) fails the bench with a non-zero status; without it, the last timed frame's hash is the verify
     render's (timed_frames_hash == framebuffer_sha256_16)."""
-    cmd = [sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--width", "96", "--spp", "4", "--no-cpu"]
+    cmd = [sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--width", "96", "--spp", "4", "--full",
+           "--no-cpu"]
     env = dict(os.environ, RTX_LIB=DBG, RTX_WATCHDOG_S="60")
     ok = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert ok.returncode == 0, ok.stdout + ok.stderr
