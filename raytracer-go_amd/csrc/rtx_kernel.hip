@@ -27,9 +27,6 @@
 #ifndef RTX_SUB_MAX  // samples per unit of a render with >= 128 units of 8 samples per resident wave
 #define RTX_SUB_MAX 16
 #endif
-#ifndef RTX_HYB_BATCH  // 1: primitive batching also for a scene in HBM with an LDS cache (A/B)
-#define RTX_HYB_BATCH 0
-#endif
 #ifndef RTX_ASM_STEP  // 1: the timed kernel's walk step in assembly (trav_step_asm); 0 for A/B
 #define RTX_ASM_STEP 1
 #endif
@@ -66,32 +63,11 @@ namespace rtxd {
 #ifndef RTX_KARG_NEAR
 #define RTX_KARG_NEAR RTX_KARG_RELOAD
 #endif
-#ifndef RTX_HYB_DRAIN  // 1: the drain also for scenes in HBM with an LDS cache (A/B; round 5: +2.3 % at config 4)
-#define RTX_HYB_DRAIN 0
-#endif
-#ifndef RTX_NT_COLOR  // 1: the sample colours stored non-temporally (A/B of the scratch's write amplification)
-#define RTX_NT_COLOR 0
-#endif
-#ifndef RTX_NEAR_AND  // 1: the near region's test reads its bounds at once (0: short-circuit form, A/B)
-#define RTX_NEAR_AND 1
-#endif
 #ifndef RTX_PRIO_WALK  // >= 0: the wave's issue priority (s_setprio) in the walk / the shading phase (A/B; -1: unset)
 #define RTX_PRIO_WALK 1
 #endif
 #ifndef RTX_PRIO_SHADE
 #define RTX_PRIO_SHADE 0
-#endif
-#ifndef RTX_PRIO_CLAIM  // >= 0: the priority from the claims on (new items, camera rays, the segment's begin; A/B)
-#define RTX_PRIO_CLAIM -1
-#endif
-#ifndef RTX_DRAIN_LDS  // 1: the drain's per-workgroup record count and far unit cursor in LDS (0: in HBM, A/B)
-#define RTX_DRAIN_LDS 1
-#endif
-#ifndef RTX_STATIC_FIRST  // 1: a wave's first unit from its grid index, no atomic (0: every unit claimed; 2: wave-major, A/B)
-#define RTX_STATIC_FIRST 1
-#endif
-#ifndef RTX_CAM_DEFER  // 1: the near pass also tests each new camera ray against the near region (the host's gate,
-#define RTX_CAM_DEFER 0  // camera_in_near, already admits only cameras whose defocus disk lies inside it)
 #endif
 // The kernel's Params as its kernel arguments hold them, behind an opaque copy of their address: a field read
 // through it is loaded (s_load) at its use instead of being kept live through the main loop, where the kernel
@@ -145,7 +121,7 @@ __device__ __forceinline__ void traverse_loop(uint32_t& mode, Trav& t, const Ray
                                               uint32_t n_entries, uint32_t thresh, Counters& cnt,
                                               uint64_t& wave_iters, uint64_t& lane_steps, uint64_t& shade_phases,
                                               uint64_t& shade_lanes, uint64_t& idle_lanes, uint64_t& parked,
-                                              uint64_t& deferred, uint32_t prim_batch, bool w2) {
+                                              uint64_t& deferred, uint32_t prim_batch) {
     // The lane modes are fixed during the phase except walking -> waiting (mode 0 -> 1) on
     // reaching the sentinel, so the votes are SALU on masks taken once: walking lanes W, waiting
     // lanes P0, lanes without an item D; per iteration only `at_end` is voted.
@@ -168,17 +144,7 @@ __device__ __forceinline__ void traverse_loop(uint32_t& mode, Trav& t, const Ray
         // the wave per step.
         uint32_t done = 0;  // COUNT: lane-steps that tested an entry (a lane on the sentinel idles)
         uint32_t idle = 0;  // COUNT: parked (low 16 bits) and deferred (high 16 bits) lane-steps
-        if (HYB && w2) {  // the paired walk's records
-#pragma unroll
-            for (int s = 0; s < STEPS; ++s) {
-                if (COUNT) {
-                    const uint32_t w = (uint32_t)__popcll(ballot(t.i < 16 * n_entries));
-                    done += w;
-                    idle += 64u - w;
-                }
-                trav_step_w2<COUNT, QUADS, MED3, FMA>(t, r, E, cnt, 16 * n_entries, no);
-            }
-        } else if constexpr (BATCH) {
+        if constexpr (BATCH) {
 #pragma unroll
             for (int s = 0; s < STEPS; ++s)
                 done += trav_step_batched<COUNT, QUADS, FIXED, HYB, MED3, FMA>(t, r, E, cnt, 16 * n_entries,
@@ -225,17 +191,17 @@ __device__ __forceinline__ void traverse_phase(uint32_t& mode, Trav& t, const Ra
                                                uint32_t n_entries, uint32_t thresh, Counters& cnt,
                                                uint64_t& wave_iters, uint64_t& lane_steps, uint64_t& shade_phases,
                                                uint64_t& shade_lanes, uint64_t& idle_lanes, uint64_t& parked,
-                                               uint64_t& deferred, uint32_t prim_batch = 0, bool w2 = false) {
+                                               uint64_t& deferred, uint32_t prim_batch = 0) {
     if (ballot(!t.safe && t.i < 16 * n_entries) == 0)
         traverse_loop<COUNT, STEPS, QUADS, FIXED, HYB, BATCH, true, FMA>(mode, t, r, E, n_entries, thresh, cnt,
                                                                        wave_iters, lane_steps, shade_phases,
                                                                        shade_lanes, idle_lanes, parked, deferred,
-                                                                       prim_batch, w2);
+                                                                       prim_batch);
     else
         traverse_loop<COUNT, STEPS, QUADS, FIXED, HYB, BATCH, false, FMA>(mode, t, r, E, n_entries, thresh, cnt,
                                                                         wave_iters, lane_steps, shade_phases,
                                                                         shade_lanes, idle_lanes, parked, deferred,
-                                                                        prim_batch, w2);
+                                                                        prim_batch);
 }
 
 enum : uint32_t { M_TRAV = 0, M_SHADE = 1, M_START = 2, M_DONE = 3, M_CLAIM = 4 };
@@ -288,8 +254,8 @@ __device__ __forceinline__ void split_clk(uint64_t& acc, uint64_t& clk) {
 // the one before stripes existed (its code unchanged: the headline kernel).
 //
 // DRAIN (render_drain): TIER 1 writes the records to the workgroup's own region of the queue
-// (Params::drain_count, drain_region); TIER 2 resumes that region's records only, its units claimed by the
-// workgroup's waves.
+// (Params::drain_region, counted in LDS at drain_lds); TIER 2 resumes that region's records only, its units claimed
+// by the workgroup's waves.
 template <bool COUNT, bool USE_LDS, bool QUADS, bool NOISE, int WAVES, bool HYB, bool CLK, int TIER, bool POOL, bool ST,
           bool DRAIN>
 __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 = 0) {
@@ -349,14 +315,10 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
     // far pass: units of 64 queue records
     // (DRAIN: this workgroup's records, written by its own waves before the barrier that ended its near phase)
     // DRAIN: the workgroup's record count and far unit cursor: two LDS words at float4 index p.drain_lds, past both
-    // phases' layouts (RTX_DRAIN_LDS), else drain_count's HBM words (a compile-time choice: a pointer that may be
-    // either would make every claim a flat atomic)
-    uint32_t* const rec_count = !DRAIN           ? p.defer_count
-                                : RTX_DRAIN_LDS ? reinterpret_cast<uint32_t*>(lds_entries + p.drain_lds)
-                                                : p.drain_count + blockIdx.x;
-    uint32_t* const far_cursor = !DRAIN           ? p.tile_counter
-                                 : RTX_DRAIN_LDS ? reinterpret_cast<uint32_t*>(lds_entries + p.drain_lds) + 1
-                                                 : p.drain_count + gridDim.x + blockIdx.x;
+    // phases' layouts (a compile-time choice between LDS and HBM: a pointer that may be either would make every
+    // claim a flat atomic)
+    uint32_t* const rec_count = !DRAIN ? p.defer_count : reinterpret_cast<uint32_t*>(lds_entries + p.drain_lds);
+    uint32_t* const far_cursor = !DRAIN ? p.tile_counter : reinterpret_cast<uint32_t*>(lds_entries + p.drain_lds) + 1;
     const uint32_t n_rec =
         TIER == 2 ? (DRAIN ? min(__builtin_amdgcn_readfirstlane(*(volatile uint32_t*)rec_count), p.drain_region)
                            : min(__builtin_amdgcn_readfirstlane(*(volatile uint32_t*)p.defer_count), p.defer_cap))
@@ -404,15 +366,9 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
 
     auto store = [&](V3 col) {  // the item's colour, GetColor's result for sample k
         float* o = p.scratch + (size_t)(rng.sample - p.k0) * tile_floats + (size_t)pix * 3;
-        if (RTX_NT_COLOR) {
-            __builtin_nontemporal_store(col.x, o);
-            __builtin_nontemporal_store(col.y, o + 1);
-            __builtin_nontemporal_store(col.z, o + 2);
-        } else {
-            o[0] = col.x;
-            o[1] = col.y;
-            o[2] = col.z;
-        }
+        o[0] = col.x;
+        o[1] = col.y;
+        o[2] = col.z;
         ++items_done;
     };
 
@@ -472,10 +428,7 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
         // (C2 +2.6 % with two such tests per phase)
         const float x0 = q.near_min[0], y0 = q.near_min[1], z0 = q.near_min[2];
         const float x1 = q.near_max[0], y1 = q.near_max[1], z1 = q.near_max[2];
-        const bool inside = RTX_NEAR_AND ? ((r.o.x >= x0) & (r.o.x <= x1) & (r.o.y >= y0) & (r.o.y <= y1) &
-                                            (r.o.z >= z0) & (r.o.z <= z1))
-                                         : (r.o.x >= x0 && r.o.x <= x1 && r.o.y >= y0 && r.o.y <= y1 &&
-                                            r.o.z >= z0 && r.o.z <= z1);
+        const bool inside = (r.o.x >= x0) & (r.o.x <= x1) & (r.o.y >= y0) & (r.o.y <= y1) & (r.o.z >= z0) & (r.o.z <= z1);
         const bool far = ready && !inside;
         defer(far);
         if (far) ready = false;
@@ -501,10 +454,9 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
         if (RTX_PRIO_WALK >= 0) __builtin_amdgcn_s_setprio(RTX_PRIO_WALK);
         // primitive batching only for a scene in LDS: a lane that waits re-reads its entry, which
         // from HBM cost config 4 +34 %
-        traverse_phase<COUNT, STEPS, QUADS, USE_LDS, HYB, USE_LDS || (RTX_HYB_BATCH && HYB), TIER == 1 && RTX_NEAR_FMA && !QUADS>(
-            mode, t, r, E, n_entries, thresh, cnt, wave_iters,
-                                                              lane_steps, shade_phases, shade_lanes, idle_lanes,
-                                                              parked, deferred, p.prim_batch, HYB && p.w2);
+        traverse_phase<COUNT, STEPS, QUADS, USE_LDS, HYB, USE_LDS, TIER == 1 && RTX_NEAR_FMA && !QUADS>(
+            mode, t, r, E, n_entries, thresh, cnt, wave_iters, lane_steps, shade_phases, shade_lanes, idle_lanes,
+            parked, deferred, p.prim_batch);
         if (TIME) {
             const uint64_t now = __builtin_amdgcn_s_memtime();
             trav_cycles += now - clk;
@@ -572,7 +524,6 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
         }
         if constexpr (TIER == 1) defer_far(ready);  // before the claims: the lane takes a new item now
         if (TIME) split_clk(split[1], clk);
-        if (RTX_PRIO_CLAIM >= 0) __builtin_amdgcn_s_setprio(RTX_PRIO_CLAIM);
         // Lanes without an item take the next ones of the wave's unit; new camera rays
         // at one program point.  Loops only for max depth 0 and ragged tiles.
         for (;;) {
@@ -581,15 +532,14 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
             if (cursor >= u_items && !exhausted && dbg_skip(p, 3u, lane)) {
                 exhausted = true;  // (debug library: the even lanes reach the claim alone)
             } else if (cursor >= u_items && !exhausted) {  // claim the next unit (wave-uniform)
-                // RTX_STATIC_FIRST (units on a global counter: TIER 0 / 1, a far launch): a wave's first unit is its grid index, the
-                // counter hands out the rest from there, so the launch does not start with every wave's atomic queued
-                // on one address (u_items is 0 only before the first claim: a claimed unit holds >= 64 items)
-                constexpr bool STATIC_FIRST = RTX_STATIC_FIRST && (TIER <= 1 || (TIER == 2 && !DRAIN));
+                // The static first unit (units on a global counter: TIER 0 / 1, a far launch): a wave's first unit is its
+                // grid index, the counter hands out the rest from there, so the launch does not start with every wave's
+                // atomic queued on one address (u_items is 0 only before the first claim: a claimed unit holds >= 64 items)
+                constexpr bool STATIC_FIRST = TIER <= 1 || (TIER == 2 && !DRAIN);
                 const uint32_t n_waves = gridDim.x * WAVES;
                 uint32_t uu;
                 if (STATIC_FIRST && u_items == 0u) {
-                    uu = __builtin_amdgcn_readfirstlane(RTX_STATIC_FIRST == 2 ? (threadIdx.x >> 6) * gridDim.x + blockIdx.x
-                                                                              : blockIdx.x * WAVES + (threadIdx.x >> 6));
+                    uu = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + (threadIdx.x >> 6));
                 } else {
                     uint32_t un = 0;
                     if (lane == 0) un = atomicAdd(DRAIN && TIER == 2 ? far_cursor : p.tile_counter, 1u);
@@ -712,8 +662,7 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
             }
         }
         // a camera ray outside the region: none, by the host's gate (rtx_capi camera_in_near: the defocus disk's box,
-        // with room for rounding, inside the region), so the test is compiled only for A/B
-        if constexpr (TIER == 1 && RTX_CAM_DEFER) defer_far(ready);
+        // with room for rounding, inside the region), so no test of the new camera rays here
         if (TIME) split_clk(split[2], clk);
         if (ready) {  // begin a segment: world.Hit (ray.go:36)
             if (COUNT) ++cnt.segments;
@@ -757,11 +706,10 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void render_items(Params p) {
 // The far phase's own settings (the rest of its Params are the near pass's): its layout and walk knobs.
 struct FarLayout {
     const float4* entries;
-    uint32_t n_entries, n_hot, start, prim_end, shade_thresh, refill_hits, prim_batch, w2;
+    uint32_t n_entries, n_hot, start, prim_end, shade_thresh, refill_hits, prim_batch;
 };
 inline FarLayout far_layout(const Params& pf) {
-    return FarLayout{pf.entries, pf.n_entries, pf.n_hot, pf.start, pf.prim_end, pf.shade_thresh, pf.refill_hits, pf.prim_batch,
-                     pf.w2};
+    return FarLayout{pf.entries, pf.n_entries, pf.n_hot, pf.start, pf.prim_end, pf.shade_thresh, pf.refill_hits, pf.prim_batch};
 }
 
 struct DrainArgs {
@@ -772,7 +720,7 @@ struct DrainArgs {
 template <bool USE_LDS, int WAVES, int MINW, bool HYB, bool POOL, bool ST, bool QUADS = false>
 __global__ __launch_bounds__(64 * WAVES, MINW) void render_drain(DrainArgs a) {
     const uint64_t t0 = __builtin_amdgcn_s_memrealtime() | 1ull;  // the watchdog's start for both phases (nonzero)
-    if constexpr (RTX_DRAIN_LDS) {  // the workgroup's two drain words in LDS (past both phases' layouts): zero first
+    {  // the workgroup's two drain words in LDS (past both phases' layouts): zero first
         extern __shared__ float4 lds_words[];
         if (threadIdx.x < 2) reinterpret_cast<uint32_t*>(lds_words + a.pn.drain_lds)[threadIdx.x] = 0u;
         __syncthreads();
@@ -794,7 +742,6 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void render_drain(DrainArgs a) {
     pf.shade_thresh = k.fl.shade_thresh;
     pf.refill_hits = k.fl.refill_hits;
     pf.prim_batch = k.fl.prim_batch;
-    pf.w2 = k.fl.w2;
     pf.tier = 2;
     render_body<false, USE_LDS, QUADS, false, WAVES, HYB, false, 2, false, false, true>(pf, t0);
 }
@@ -810,10 +757,11 @@ __global__ __launch_bounds__(256) void spill_redo_list(Params p) {
 }
 
 // A tiered chunk's counters, zeroed by one launch before its near pass (four memsets cost C1 ~20 us of launch gaps):
-// the unit queue head, the record count, the redo list count, the drain's per-workgroup words [0, n_drain), and the
-// far and redo passes' own unit queue heads (DRAIN_WORDS - 2, - 1); for the render's first chunk (first != 0) every
-// stats slot too (rtx_capi's enqueue_on leaves them to this launch for a tiered render).
-__global__ __launch_bounds__(256) void chunk_start(Params p, uint32_t n_drain, uint32_t first) {
+// the unit queue head, the record count, the redo list count, and the far and redo passes' own unit queue heads
+// (drain_count's words DRAIN_WORDS - 2, - 1; the drain's per-workgroup words are in LDS, zeroed by render_drain); for
+// the render's first chunk (first != 0) every stats slot too (rtx_capi's enqueue_on leaves them to this launch for a
+// tiered render).
+__global__ __launch_bounds__(256) void chunk_start(Params p, uint32_t first) {
     if (first)
         for (uint32_t i = threadIdx.x; i < COUNTER_SLOTS; i += 256) p.counters[i] = 0ull;
     __syncthreads();  // (the unit queue head and the record count share the slots)
@@ -824,7 +772,6 @@ __global__ __launch_bounds__(256) void chunk_start(Params p, uint32_t n_drain, u
         p.drain_count[DRAIN_WORDS - 2] = 0u;
         p.drain_count[DRAIN_WORDS - 1] = 0u;
     }
-    for (uint32_t i = threadIdx.x; i < n_drain; i += 256) p.drain_count[i] = 0u;
 }
 
 // GetPixelColor's sum over the stored colours of samples [k0, k0 + kn), in k order
@@ -1000,12 +947,12 @@ hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream) {
     // The drain (render_drain, the timed kernels): the near grid's workgroups resume their own records in the
     // same LDS (the larger of the two layouts), when that keeps the near pass's occupancy.
     // (Not for a scene in HBM with LDS caches: the combined kernel spilled 24 VGPRs there, and config 4 took +2.3 %.)
-    constexpr bool CAN_DRAIN = !COUNT && !CLK && (!HYB || RTX_HYB_DRAIN);
+    constexpr bool CAN_DRAIN = !COUNT && !CLK && !HYB;
     const void* kd = nullptr;
     if constexpr (CAN_DRAIN) kd = (const void*)render_drain<USE_LDS, WN, MN, HYB, POOL, ST, QUADS>;
-    // (RTX_DRAIN_LDS: the drain's two per-workgroup words in LDS after the larger layout)
-    const size_t sl = ((sn > sf ? sn : sf) + 15) / 16 * 16, sd = RTX_DRAIN_LDS ? sl + 16 : sl;
-    pn.drain_lds = RTX_DRAIN_LDS ? (uint32_t)(sl / 16) : 0u;
+    // (the drain's two per-workgroup words in LDS after the larger layout)
+    const size_t sl = ((sn > sf ? sn : sf) + 15) / 16 * 16, sd = sl + 16;
+    pn.drain_lds = (uint32_t)(sl / 16);
     int per_d = 0;
     bool drain = CAN_DRAIN && pn.drain && pn.drain_count;
     if (drain && (e = resident_grid(kd, block_n, sd, &per_d, &cus)) != hipSuccess) return e;
@@ -1035,8 +982,7 @@ hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream) {
         // that set any); with the drain each workgroup's region is the queue over the near grid (a region that fills
         // sends the rest to the redo pass)
         const bool drain_now = drain && 2 * bn + 2 <= DRAIN_WORDS;
-        hipLaunchKernelGGL(chunk_start, dim3(1), dim3(256), 0, stream, pn, drain_now ? (uint32_t)(2 * bn) : 0u,
-                           (uint32_t)(k0 == 0));
+        hipLaunchKernelGGL(chunk_start, dim3(1), dim3(256), 0, stream, pn, (uint32_t)(k0 == 0));
         if (drain_now) {
             pn.drain_region = pf.drain_region = pn.defer_cap / (uint32_t)bn;
             if constexpr (CAN_DRAIN)
@@ -1103,7 +1049,6 @@ hipError_t launch_render_t(const Params& p, uint32_t flags, hipStream_t stream, 
     const bool count = (flags & RTX_FLAG_COUNTERS) != 0;
     if (far) {  // the caller checked: spheres only, both layouts placed alike (tier_placement), no noise
         const uint32_t place = tier_placement(p, *far, flags);
-        if ((p.w2 || far->w2) && place != RTX_SCENE_LDS_CACHE) return hipErrorInvalidValue;  // (records: cache kernels)
         if (p.tier != 1 || far->tier != 2 || !p.defer || !far->defer || !p.redo_bits || p.has_noise)
             return hipErrorInvalidValue;
         if (p.n_quads) {  // quads: single-row shards, the timed and counting kernels (rtx_capi's enqueue_on)
@@ -1142,7 +1087,6 @@ hipError_t launch_render_t(const Params& p, uint32_t flags, hipStream_t stream, 
                      : launch_tiered<false, V, MV, false, false, false, false, ST>(p, *far, stream);
     }
     const bool use_lds = scene_placement(p, flags) == RTX_SCENE_IN_LDS;
-    if (p.w2 && scene_placement(p, flags) != RTX_SCENE_LDS_CACHE) return hipErrorInvalidValue;  // (records: cache kernels)
     if (!count && (flags & RTX_FLAG_TIMING) && !p.has_noise && p.item_waves != 4)  // diagnostics: sphere scenes
         return p.n_quads ? launch_items<false, true, false, RTX_V3_WAVES, RTX_V3_MINW, true, false, ST>(p, use_lds, stream)
                          : launch_items<false, false, false, RTX_V3_WAVES, RTX_V3_MINW, true, false, ST>(p, use_lds, stream);
