@@ -45,6 +45,7 @@ import (
 type gpuConfig struct {
 	gpus     int
 	seed     uint64
+	noiseTol float32     // WithNoiseTolerance: RenderProgressive stops once no pixel is noisier (0: off)
 	fallback atomic.Bool // RenderGPU is running the CPU Render: the hook stays out of the way
 }
 
@@ -77,6 +78,15 @@ func WithGPUs(n int) CameraOpt {
 func WithSeed(seed uint64) CameraOpt {
 	return func(c *Camera) {
 		c.gpuConfig().seed = seed
+	}
+}
+
+// WithNoiseTolerance makes RenderProgressive stop as soon as no pixel is noisy at the relative
+// tolerance rel (rtx_accum_resolve: the summed variance of the pixel mean against (rel * max(r + g + b,
+// 0.01))^2), before samplesPerPixel is reached.  0, the default, renders every sample.
+func WithNoiseTolerance(rel float32) CameraOpt {
+	return func(c *Camera) {
+		c.gpuConfig().noiseTol = rel
 	}
 }
 
@@ -445,6 +455,77 @@ func sceneOf(world Hittable, seed uint64) (*C.rtx_scene, error) {
 	return scene, nil
 }
 
+// gpuCamera is Camera.init's derived state (camera.go:128-165) as rtx.h's kernel constants.
+func (c *Camera) gpuCamera() C.rtx_camera {
+	return C.rtx_camera{
+		image_width: C.uint32_t(c.imageWidth), image_height: C.uint32_t(c.imageHeight),
+		samples_per_pixel: C.uint32_t(c.samplesPerPixel), max_depth: C.uint32_t(max(c.bounceDepth, 0)),
+		center: vec(c.center), defocus_angle: C.float(c.defocusAngleRadians),
+		pixel00: vec(c.pixel00), pixel_du: vec(c.pixelDu), pixel_dv: vec(c.pixelDv),
+		defocus_disk_u: vec(c.defocusDiskU), defocus_disk_v: vec(c.defocusDiskV),
+		background: vec(c.background.GetColor()),
+	}
+}
+
+// RenderProgressive is Render on one MI355X in passes of passSamples samples per pixel (rtx_accum,
+// rtx.h "progressive rendering"): after every pass onPass (when not nil) is told the samples done
+// and the pixels still noisy at WithNoiseTolerance's tolerance, and returning false stops the render
+// there.  It ends at samplesPerPixel, when onPass says so, or, with WithNoiseTolerance, when no pixel
+// is noisy, and writes the P3 bytes of the image so far: after n samples exactly the bytes a Render
+// with samplesPerPixel = n writes.  onPass runs between two C calls, on the caller's goroutine: no C
+// code calls back into Go.  A scene the GPU path does not carry is an error here (there is no CPU
+// path that stops early).
+func (c *Camera) RenderProgressive(world Hittable, writer io.Writer, passSamples int, onPass func(done int, noisy uint64) bool) error {
+	c.init()
+	cfg := c.gpuConfig()
+	if passSamples <= 0 {
+		passSamples = c.samplesPerPixel
+	}
+	scene, err := sceneOf(world, cfg.seed)
+	if err != nil {
+		return err
+	}
+	defer C.rtx_scene_destroy(scene) // (deferred calls run last in, first out: the accumulator goes first)
+	cam := c.gpuCamera()
+	region := C.rtx_region{x0: 0, y0: 0, width: cam.image_width, height: cam.image_height, rank: 0, world: 1, stripe: 0}
+	var acc *C.rtx_accum
+	if rc := C.rtx_accum_create(scene, &cam, C.uint64_t(cfg.seed), &region, &acc); rc != 0 {
+		return rtxErr(rc)
+	}
+	defer C.rtx_accum_destroy(acc)
+	for done := 0; done < c.samplesPerPixel; {
+		count := min(passSamples, c.samplesPerPixel-done)
+		// the default stream orders the passes and the resolves of this accumulator
+		if rc := C.rtx_accum_add(acc, C.uint32_t(count), nil, 0, nil); rc != 0 {
+			return rtxErr(rc)
+		}
+		done = int(C.rtx_accum_samples(acc))
+		if onPass == nil && cfg.noiseTol <= 0 {
+			continue // nobody looks at the image before the end: the passes stay enqueued back to back
+		}
+		var noisy C.uint64_t
+		if rc := C.rtx_accum_resolve(acc, nil, nil, C.float(cfg.noiseTol), &noisy); rc != 0 {
+			return rtxErr(rc)
+		}
+		if onPass != nil && !onPass(done, uint64(noisy)) {
+			break
+		}
+		if cfg.noiseTol > 0 && noisy == 0 {
+			break
+		}
+	}
+	text := make([]byte, int(C.rtx_ppm_max_bytes(cam.image_width, cam.image_height)))
+	var n C.uint64_t
+	if rc := C.rtx_accum_ppm(acc, (*C.char)(unsafe.Pointer(&text[0])), C.uint64_t(len(text)), &n); rc != 0 {
+		return rtxErr(rc)
+	}
+	if rc := C.rtx_device_check(0); rc != 0 { // the passes ran without stats: the sticky error word, once
+		return rtxErr(rc)
+	}
+	_, err = writer.Write(text[:int(n)])
+	return err
+}
+
 // renderOnDevices renders on `gpus` devices and writes Render's P3 bytes; errFallback when the GPU
 // path cannot carry the render (nothing has been written then).
 func (c *Camera) renderOnDevices(world Hittable, writer io.Writer, seed uint64, gpus int) error {
@@ -462,14 +543,7 @@ func (c *Camera) renderOnDevices(world Hittable, writer io.Writer, seed uint64, 
 	defer C.rtx_scene_destroy(scene)
 
 	w, h := int(c.imageWidth), int(c.imageHeight)
-	cam := C.rtx_camera{
-		image_width: C.uint32_t(w), image_height: C.uint32_t(h),
-		samples_per_pixel: C.uint32_t(c.samplesPerPixel), max_depth: C.uint32_t(max(c.bounceDepth, 0)),
-		center: vec(c.center), defocus_angle: C.float(c.defocusAngleRadians),
-		pixel00: vec(c.pixel00), pixel_du: vec(c.pixelDu), pixel_dv: vec(c.pixelDv),
-		defocus_disk_u: vec(c.defocusDiskU), defocus_disk_v: vec(c.defocusDiskV),
-		background: vec(c.background.GetColor()),
-	}
+	cam := c.gpuCamera()
 	// Render + the P3 text (header included) on the device: rtx_render_ppm on the current device for one
 	// GPU; for several, rtx_render_ppm_ex (ABI 9) gathers the row-interleaved bands to device 0 over RCCL
 	// and encodes them there, so no per-pixel formatting runs on the host at any device count

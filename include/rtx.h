@@ -490,6 +490,83 @@ int rtx_render_ppm(rtx_scene* scene, const rtx_camera* cam, uint64_t seed, char*
 int rtx_render_ppm_ex(rtx_scene* scene, const rtx_camera* cam, uint64_t seed, int n_gpus, char* out_text,
                       uint64_t capacity, uint64_t* out_len, rtx_stats* stats);
 
+/* ---- progressive rendering (ABI 10, additive) -------------------
+ * rtx_render* run samples_per_pixel samples in one blocking call (camera.go:256-261).  An
+ * rtx_accum renders them in PASSES of the caller's size and can be looked at in between: after n
+ * accumulated samples the resolved image is, bit for bit, what a one-shot render of the same
+ * region with samples_per_pixel = n returns, for every n and any split into passes.
+ *
+ * An accumulator belongs to one scene, one device (the device current at create) and one
+ * (camera, seed, region), all copied at create; the camera's samples_per_pixel is not used by it
+ * (a host wrapper uses it as its target).  Per pixel of the region's shard it holds float32
+ * S[3] and Q[3], and n, the samples done: all zero at create and after reset.  A pass adds, for
+ * every pixel and channel, in k order:  S = S + c;  Q = Q + c * c  (the product rounded to
+ * float32 before the add), c being the colour the one-shot render computes for sample k.
+ *
+ * Rules
+ *  - The caller orders the passes and resolves of ONE accumulator: the same stream, or a
+ *    synchronise between them.  Different accumulators are independent.
+ *  - Accumulators are destroyed before their scene.
+ *  - A call with another device current than the accumulator's returns RTX_ERR_INVALID_ARG.
+ *  - S and Q belong to the accumulator, not to the per-device scratch: other renders on the
+ *    device do not disturb them, rtx_device_scratch_bytes does not count them and
+ *    rtx_release_device_memory does not touch accumulators.
+ *  - Several GPUs work as for rtx_render_region_device: one accumulator per rank's shard, on
+ *    that rank's device; shards are independent.
+ *  - The variance is Q/n - mean^2, which cancels: its error is about n * 2^-24 of mean^2, so on
+ *    a constant pixel it comes out as a small value of either sign and is clamped at 0 (323 of
+ *    the 3888 channel values of randSpheres 48x27 at 8 samples, all on constant sky).          */
+typedef struct rtx_accum rtx_accum;
+
+/* Validates as rtx_render_region_device does; allocates and zeroes 24 B per pixel slot of the
+ * region's shard (64-pixel tiles, ragged tiles padded) on the current device. */
+int rtx_accum_create(rtx_scene* scene, const rtx_camera* cam, uint64_t seed, const rtx_region* region,
+                     rtx_accum** out);
+
+/* One pass: renders samples k = n .. n + count - 1 of every pixel on hip_stream and sets
+ * n += count.  count == 0, or n + count past 2^32 - 1, returns RTX_ERR_INVALID_ARG.  flags as for
+ * rtx_render_region_device.  Returns after enqueueing unless stats != NULL; then it synchronises
+ * and fills stats for THIS pass: samples = pixels * count, sample_chunks, kernel_ms, walk_layout,
+ * and with RTX_FLAG_COUNTERS the work counters of this pass alone.  The sticky error word works
+ * as for any render (rtx_device_check). */
+int rtx_accum_add(rtx_accum* accum, uint32_t count, void* hip_stream, uint32_t flags, rtx_stats* stats);
+
+/* n, the samples accumulated per pixel (0 for NULL). */
+uint32_t rtx_accum_samples(const rtx_accum* accum);
+
+/* The image after n >= 1 samples into device memory, on hip_stream: d_rgb, and d_var when not
+ * NULL, hold the region's compacted shard rows (rtx_region), row-major, 3 floats per pixel.  All
+ * arithmetic is float32, each operation rounded (no fused multiply-add, no square root):
+ *     inv   = 1.0f / (float)n
+ *     rgb_c = S_c * inv
+ *     d     = Q_c * inv - rgb_c * rgb_c
+ *     v     = d > 0 ? d : 0                       (a NaN gives 0)
+ *     var_c = v * inv                             the biased variance of the pixel mean
+ *     sv    = (var_r + var_g) + var_b
+ *     mb    = (rgb_r + rgb_g) + rgb_b
+ *     t     = rel_tol * (mb > 0.01f ? mb : 0.01f)
+ * and a pixel is NOISY when sv > t * t.  *noisy (when not NULL) receives the number of noisy
+ * pixels, and the call then synchronises the stream; else it returns after enqueueing.  The
+ * accumulator is not modified: more passes may follow. */
+int rtx_accum_resolve_device(rtx_accum* accum, float* d_rgb, float* d_var, float rel_tol, void* hip_stream,
+                             uint64_t* noisy);
+
+/* The same into host memory, after every render enqueued on the device so far.  out_var and noisy
+ * may be NULL; so may out_rgb when noisy is not (the count alone: a stopping rule that needs no
+ * image).  Blocking. */
+int rtx_accum_resolve(rtx_accum* accum, float* out_rgb, float* out_var, float rel_tol, uint64_t* noisy);
+
+/* Resolve, rtx_encode_ppm_device, and the text copied to the caller's host buffer (capacity at
+ * least rtx_ppm_max_bytes(region width, shard rows)).  For a whole-image region the bytes equal
+ * rtx_render_ppm's at samples_per_pixel = n.  Blocking. */
+int rtx_accum_ppm(rtx_accum* accum, char* out_text, uint64_t capacity, uint64_t* out_len);
+
+/* Back to n = 0 with S and Q zero, after everything enqueued on the device.  Blocking. */
+int rtx_accum_reset(rtx_accum* accum);
+
+/* Frees the accumulator's device memory (NULL is a no-op).  Blocking. */
+void rtx_accum_destroy(rtx_accum* accum);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@
 #include <limits>
 #include <map>
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -272,7 +273,7 @@ void release_comms_locked() {  // g_rccl_mu held
 // rtx_render's per-device buffers (bands, the gathered bands, the assembled image), stream and
 // gather events, kept between calls and freed by rtx_release_device_memory; g_render_mu is held
 // for a whole rtx_render.  Keyed by (device, slot): slot d >= 0 is band d, -1 the gather, -2 the
-// image.
+// image, -3 / -4 the image and text of rtx_render_ppm and rtx_accum_ppm, -5 rtx_accum_resolve's variance.
 struct RenderBuf {
     void* ptr = nullptr;
     size_t bytes = 0;
@@ -1016,8 +1017,12 @@ rtxd::Params make_params(const rtx_scene* s, const DeviceCopy* c, uint32_t oct, 
 // Enqueue one region on the current device, bracketed by HIP events on `stream`.
 // *chunks receives the number of sample chunks (render kernel launches).
 // *tiered: whether the render walks in two tiers.
+// pass: one pass of an accumulator (its samples into its S and Q, d_out unused; pass_slots: the scratch slots its
+// buffers hold) instead of the camera's samples_per_pixel averaged into d_out.
 int enqueue_on(rtx_scene* s, DeviceCopy* c, const rtx_camera* cam, uint64_t seed, const rtx_region* r, float* d_out,
-               hipStream_t stream, uint32_t flags, bool timed, uint32_t* chunks, bool* tiered) {
+               hipStream_t stream, uint32_t flags, bool timed, uint32_t* chunks, bool* tiered,
+               const rtxd::SampleRange* pass = nullptr, uint64_t pass_slots = 0) {
+    const uint32_t n_samples = pass ? pass->count : cam->samples_per_pixel;  // of every pixel, in this call
     const uint32_t oct = layout_slot(s, cam);  // the walk's layout (rtx_topology.h, rtx_collapse.h)
     if (int rc = ensure_layout(s, c, cam)) return rc;
     rtxd::Params p = make_params(s, c, oct, cam, seed, r, d_out);
@@ -1047,9 +1052,13 @@ int enqueue_on(rtx_scene* s, DeviceCopy* c, const rtx_camera* cam, uint64_t seed
         // tile-major: every tile of 64 pixels whole (render_items / reduce_samples), 12 B per pixel
         const uint64_t per_sample =
             (uint64_t)rtxd::tiles_x_of(p.width, p.tile_w_log2) * rtxd::tiles_y_of(p.rows, p.tile_w_log2) * 64 * 12;
+        // an accumulator's S and Q were sized at create: the tiles must be the same (RTX_TILE_W changed since?)
+        if (pass && per_sample / 12 != pass_slots)
+            return fail(RTX_ERR_INVALID_ARG, "the accumulator holds %llu pixel slots, this pass has %llu (RTX_TILE_W changed?)",
+                        (unsigned long long)pass_slots, (unsigned long long)(per_sample / 12));
         const uint64_t budget = (uint64_t)env_knob("RTX_SCRATCH_MB", 16384, 1, 1 << 20) << 20;
         uint64_t chunk = budget / per_sample;
-        if (chunk > cam->samples_per_pixel) chunk = cam->samples_per_pixel;
+        if (chunk > n_samples) chunk = n_samples;
         // the tiered walk names a chunk's samples by 32-bit ids ((k - k0) * tiles * 64 + slot: the redo
         // list, the redo bits' index): at most 2^32 scratch slots per chunk
         if (tier) chunk = std::min<uint64_t>(chunk, 0xFFFFFFFFull / (per_sample / 12));
@@ -1065,7 +1074,7 @@ int enqueue_on(rtx_scene* s, DeviceCopy* c, const rtx_camera* cam, uint64_t seed
         }
         p.scratch = scr->ptr;
         p.kn = (uint32_t)chunk;
-        *chunks = (uint32_t)((cam->samples_per_pixel + chunk - 1) / chunk);
+        *chunks = (uint32_t)((n_samples + chunk - 1) / chunk);
         p.sub = env_knob("RTX_ITEM_SUB", 0, 0, 4096);  // 0: chosen per chunk by launch_items
         // the redo pass skips a unit by one vote over its samples' bit words, one sample per lane
         if (tier && p.sub > 64) p.sub = 64;
@@ -1156,7 +1165,8 @@ int enqueue_on(rtx_scene* s, DeviceCopy* c, const rtx_camera* cam, uint64_t seed
     // launch zeroes them: one launch fewer); the sticky error word is not among them
     if (!*tiered) HIP_TRY(hipMemsetAsync(c->counters, 0, rtxd::COUNTER_SLOTS * sizeof(unsigned long long), stream));
     if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
-    if (const hipError_t e = *tiered ? rtxd::launch_render(pn, flags, stream, &p) : rtxd::launch_render(p, flags, stream)) {
+    if (const hipError_t e = *tiered ? rtxd::launch_render(pn, flags, stream, &p, pass)
+                                     : rtxd::launch_render(p, flags, stream, nullptr, pass)) {
         scr->redo_zero = 0;  // a chunk may have stopped between setting redo bits and clearing them
         return fail(e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP, "render launch failed: %s", hipGetErrorString(e));
     }
@@ -1958,6 +1968,215 @@ int rtx_render_ppm_ex(rtx_scene* s, const rtx_camera* cam, uint64_t seed, int n_
     (void)hipSetDevice(cur);
     if (rc == RTX_OK) *out_len = len;
     return rc;
+}
+
+}  // extern "C"
+
+// ---- progressive rendering (ABI 10, additive) ------------------------------------------------
+// One (scene, device, camera, seed, region): the running sums S and Q of its shard's sample colours, tile-major
+// (rtx_kernel.hip accumulate_samples), owned by the accumulator and not part of the per-device scratch, and the
+// samples done.
+struct rtx_accum {
+    rtx_scene* scene = nullptr;
+    int device = -1;
+    rtx_camera cam;
+    uint64_t seed = 0;
+    rtx_region region;
+    uint32_t rows = 0;         // region_rows(&region)
+    uint32_t tile_w_log2 = 0;  // the tiles S and Q are laid out in (make_params)
+    uint64_t slots = 0;        // tiles x 64
+    float* s = nullptr;        // slots x 3 floats, then Q's slots x 3 (one allocation)
+    float* q = nullptr;
+    unsigned long long* noisy = nullptr;  // resolve_accum's count
+    uint32_t n = 0;
+};
+
+namespace {
+// The accumulator's device is the current one (every entry that touches its memory).
+int accum_device(const rtx_accum* a) {
+    int cur = 0;
+    HIP_TRY(hipGetDevice(&cur));
+    if (cur != a->device)
+        return fail(RTX_ERR_INVALID_ARG, "the accumulator lives on device %d, the current device is %d", a->device, cur);
+    return RTX_OK;
+}
+size_t accum_bytes(const rtx_accum* a) { return (size_t)a->slots * 3 * sizeof(float); }  // of S, and of Q
+
+// rtx_accum_resolve_device with a->scene->mu held.
+int accum_resolve_locked(rtx_accum* a, float* d_rgb, float* d_var, float rel_tol, hipStream_t st, uint64_t* noisy) {
+    if (noisy) HIP_TRY(hipMemsetAsync(a->noisy, 0, sizeof(unsigned long long), st));
+    const rtxd::ResolveArgs ra{a->s, a->q, d_rgb, d_var, noisy ? a->noisy : nullptr, a->region.width, a->rows,
+                               a->tile_w_log2, a->n, rel_tol};
+    HIP_TRY(rtxd::launch_resolve(ra, st));
+    if (noisy) {
+        unsigned long long h = 0;
+        HIP_TRY(hipMemcpyAsync(&h, a->noisy, sizeof(h), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        *noisy = h;
+    }
+    return RTX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rtx_accum_create(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const rtx_region* region, rtx_accum** out) {
+    g_last_error.clear();
+    if (!s || !out) return fail(RTX_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = check_camera(cam)) return rc;
+    if (int rc = check_region(cam, region)) return rc;
+    int cur = 0;
+    HIP_TRY(hipGetDevice(&cur));
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceCopy* c = nullptr;
+    if (int rc = ensure_device(s, cur, &c)) return rc;
+    HIP_TRY(hipSetDevice(cur));
+    rtx_accum* a = new (std::nothrow) rtx_accum();
+    if (!a) return fail(RTX_ERR_OOM, "host memory for an accumulator");
+    a->scene = s;
+    a->device = cur;
+    a->cam = *cam;
+    a->seed = seed;
+    a->region = *region;
+    a->rows = region_rows(region);
+    a->tile_w_log2 = make_params(s, c, layout_slot(s, cam), cam, seed, region, nullptr).tile_w_log2;
+    a->slots = (uint64_t)rtxd::tiles_x_of(region->width, a->tile_w_log2) * rtxd::tiles_y_of(a->rows, a->tile_w_log2) * 64;
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, std::max<size_t>(2 * accum_bytes(a), sizeof(float)));
+    if (e == hipSuccess) e = hipMemset(p, 0, std::max<size_t>(2 * accum_bytes(a), sizeof(float)));
+    void* nz = nullptr;
+    if (e == hipSuccess) e = hipMalloc(&nz, sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        if (p) (void)hipFree(p);
+        delete a;
+        return fail(e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP, "the accumulator's buffers: %s", hipGetErrorString(e));
+    }
+    a->s = static_cast<float*>(p);
+    a->q = a->s + a->slots * 3;
+    a->noisy = static_cast<unsigned long long*>(nz);
+    *out = a;
+    return RTX_OK;
+}
+
+int rtx_accum_add(rtx_accum* a, uint32_t count, void* hip_stream, uint32_t flags, rtx_stats* stats) {
+    g_last_error.clear();
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    if (count == 0) return fail(RTX_ERR_INVALID_ARG, "a pass of 0 samples");
+    if (a->n + count < a->n) return fail(RTX_ERR_INVALID_ARG, "%u + %u samples exceed 2^32 - 1", a->n, count);
+    if (int rc = accum_device(a)) return rc;
+    rtx_scene* s = a->scene;
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceCopy* c = nullptr;
+    if (int rc = ensure_device(s, a->device, &c)) return rc;
+    HIP_TRY(hipSetDevice(a->device));
+    const rtxd::SampleRange pass{a->n, count, a->s, a->q};
+    uint32_t chunks = 0;
+    bool tiered = false;
+    if (int rc = enqueue_on(s, c, &a->cam, a->seed, &a->region, nullptr, (hipStream_t)hip_stream, flags, stats != nullptr,
+                            &chunks, &tiered, &pass, a->slots))
+        return rc;
+    a->n += count;
+    if (!stats) return RTX_OK;
+    const int rc = collect_on(c, (flags & RTX_FLAG_COUNTERS) != 0, (uint64_t)a->rows * a->region.width * count, chunks, stats);
+    stats->walk_layout = walk_layout(s, &a->cam, tiered);
+    return rc;
+}
+
+uint32_t rtx_accum_samples(const rtx_accum* a) { return a ? a->n : 0u; }
+
+int rtx_accum_resolve_device(rtx_accum* a, float* d_rgb, float* d_var, float rel_tol, void* hip_stream, uint64_t* noisy) {
+    g_last_error.clear();
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    if (!d_rgb && (uint64_t)a->rows * a->region.width) return fail(RTX_ERR_INVALID_ARG, "NULL output");
+    if (a->n == 0) return fail(RTX_ERR_INVALID_ARG, "nothing accumulated yet");
+    if (int rc = accum_device(a)) return rc;
+    std::lock_guard<std::mutex> lk(a->scene->mu);
+    return accum_resolve_locked(a, d_rgb, d_var, rel_tol, (hipStream_t)hip_stream, noisy);
+}
+
+int rtx_accum_resolve(rtx_accum* a, float* out_rgb, float* out_var, float rel_tol, uint64_t* noisy) {
+    g_last_error.clear();
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    const size_t bytes = (size_t)a->rows * a->region.width * 3 * sizeof(float);
+    if (!out_rgb && !noisy) return fail(RTX_ERR_INVALID_ARG, "NULL output");  // (out_rgb NULL: the count alone)
+    if (a->n == 0) return fail(RTX_ERR_INVALID_ARG, "nothing accumulated yet");
+    if (int rc = accum_device(a)) return rc;
+    std::lock_guard<std::mutex> lk(a->scene->mu);
+    std::lock_guard<std::mutex> bl(g_render_mu);  // the cached image buffers and stream
+    hipStream_t st = render_stream(a->device);
+    float* rgb = static_cast<float*>(render_buffer(a->device, -3, std::max<size_t>(1, bytes)));
+    float* var = out_var ? static_cast<float*>(render_buffer(a->device, -5, std::max<size_t>(1, bytes))) : nullptr;
+    if (!st) return fail(RTX_ERR_HIP, "stream on device %d", a->device);
+    if (!rgb || (out_var && !var)) return fail(RTX_ERR_OOM, "device buffers for a %ux%u resolve", a->region.width, a->rows);
+    // the passes may have run on any stream: every render on the device precedes the resolve (scr->last)
+    {
+        std::lock_guard<std::mutex> sl(g_scratch_mu);
+        Scratch& scr = g_scratch[a->device];
+        if (scr.last) HIP_TRY(hipStreamWaitEvent(st, scr.last, 0));
+    }
+    int rc = accum_resolve_locked(a, rgb, var, rel_tol, st, noisy);
+    if (rc == RTX_OK && bytes && out_rgb && copy_to_host(out_rgb, rgb, bytes, st) != hipSuccess)
+        rc = fail(RTX_ERR_HIP, "copying the resolved image to the host");
+    if (rc == RTX_OK && bytes && out_var && copy_to_host(out_var, var, bytes, st) != hipSuccess)
+        rc = fail(RTX_ERR_HIP, "copying the variance to the host");
+    (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+int rtx_accum_ppm(rtx_accum* a, char* out_text, uint64_t capacity, uint64_t* out_len) {
+    g_last_error.clear();
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    if (!out_text || !out_len) return fail(RTX_ERR_INVALID_ARG, "NULL argument");
+    if (a->n == 0) return fail(RTX_ERR_INVALID_ARG, "nothing accumulated yet");
+    if (int rc = accum_device(a)) return rc;
+    const uint32_t W = a->region.width, H = a->rows;
+    const uint64_t need = rtxd::ppm_max_bytes(W, H);
+    std::lock_guard<std::mutex> lk(a->scene->mu);
+    std::lock_guard<std::mutex> bl(g_render_mu);
+    hipStream_t st = render_stream(a->device);
+    float* rgb = static_cast<float*>(render_buffer(a->device, -3, std::max<size_t>(1, (size_t)W * H * 3 * sizeof(float))));
+    char* text = static_cast<char*>(render_buffer(a->device, -4, need));
+    if (!st) return fail(RTX_ERR_HIP, "stream on device %d", a->device);
+    if (!rgb || !text) return fail(RTX_ERR_OOM, "device buffers for a %ux%u PPM", W, H);
+    {
+        std::lock_guard<std::mutex> sl(g_scratch_mu);
+        Scratch& scr = g_scratch[a->device];
+        if (scr.last) HIP_TRY(hipStreamWaitEvent(st, scr.last, 0));
+    }
+    int rc = accum_resolve_locked(a, rgb, nullptr, 0.0f, st, nullptr);
+    uint64_t len = 0;
+    if (rc == RTX_OK) rc = rtx_encode_ppm_device(rgb, W, H, text, need, &len, st);
+    if (rc == RTX_OK && len > capacity) rc = fail(RTX_ERR_INVALID_ARG, "capacity %llu < PPM length %llu",
+                                                  (unsigned long long)capacity, (unsigned long long)len);
+    if (rc == RTX_OK && copy_to_host(out_text, text, len, st) != hipSuccess)
+        rc = fail(RTX_ERR_HIP, "copying the PPM text to the host");
+    (void)hipStreamSynchronize(st);
+    if (rc == RTX_OK) *out_len = len;
+    return rc;
+}
+
+int rtx_accum_reset(rtx_accum* a) {
+    g_last_error.clear();
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    if (int rc = accum_device(a)) return rc;
+    std::lock_guard<std::mutex> lk(a->scene->mu);
+    HIP_TRY(hipDeviceSynchronize());  // passes and resolves in flight, on any stream
+    HIP_TRY(hipMemset(a->s, 0, std::max<size_t>(2 * accum_bytes(a), sizeof(float))));
+    a->n = 0;
+    return RTX_OK;
+}
+
+void rtx_accum_destroy(rtx_accum* a) {
+    if (!a) return;
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    if (hipSetDevice(a->device) == hipSuccess) {
+        (void)hipDeviceSynchronize();
+        if (a->s) (void)hipFree(a->s);
+        if (a->noisy) (void)hipFree(a->noisy);
+    }
+    (void)hipSetDevice(cur);
+    delete a;
 }
 
 }  // extern "C"

@@ -841,6 +841,130 @@ __global__ __launch_bounds__(256) void reduce_samples(Params p, uint32_t last) {
     o[2] = sz;
 }
 
+// reduce_samples' sibling for an accumulator (rtx_accum): the chunk's colours added, in k order, to the
+// running first and second moments S and Q, never scaled (rtx_accum_resolve divides).  Same thread <-> scratch slot
+// mapping and loads; S and Q are tile-major like the scratch (slot i at float offset 3 i, ragged tiles padded and left
+// zero), so a wave reads and writes 768 contiguous bytes of each, once per chunk.  Always a continuation: the buffers
+// are zero at create and after reset.  c * c is rounded to float32 before the add (__fmul_rn: never contracted).
+// It clears the chunk's redo bits as reduce_samples does.
+__global__ __launch_bounds__(256) void accumulate_samples(Params p, float* acc_s, float* acc_q) {
+    const uint32_t twl = p.tile_w_log2;
+    const uint32_t tiles_x = tiles_x_of(p.width, twl);
+    const size_t n_tiles = (size_t)tiles_x * tiles_y_of(p.rows, twl);
+    if (p.redo_count && __builtin_amdgcn_readfirstlane(*(volatile uint32_t*)p.redo_count) > p.redo_cap) {
+        const uint64_t words = (uint64_t)p.kn * n_tiles * 2;  // 64 bits a tile
+        for (uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x; w < words; w += (uint64_t)gridDim.x * 256)
+            p.redo_bits[w] = 0u;
+    }
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_tiles * 64) return;
+    const uint32_t t = (uint32_t)(i >> 6), l = (uint32_t)(i & 63u);
+    const uint32_t lx = ((t % tiles_x) << twl) + (l & ((1u << twl) - 1u)), lr = (t / tiles_x) * (64u >> twl) + (l >> twl);
+    if (lx >= p.width || lr >= p.rows) return;  // outside a ragged tile: its S and Q stay zero
+    float* s = acc_s + i * 3;
+    float* q = acc_q + i * 3;
+    float sx = s[0], sy = s[1], sz = s[2];
+    float qx = q[0], qy = q[1], qz = q[2];
+    const float* src = p.scratch + i * 3;
+    const size_t stride = n_tiles * 64 * 3;
+    uint32_t k = 0;
+    for (; k + 8 <= p.kn; k += 8, src += 8 * stride) {
+        float c[8][3];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {  // (read once: non-temporal)
+            c[j][0] = __builtin_nontemporal_load(src + j * stride);
+            c[j][1] = __builtin_nontemporal_load(src + j * stride + 1);
+            c[j][2] = __builtin_nontemporal_load(src + j * stride + 2);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            sx = sx + c[j][0];
+            sy = sy + c[j][1];
+            sz = sz + c[j][2];
+            qx = qx + __fmul_rn(c[j][0], c[j][0]);
+            qy = qy + __fmul_rn(c[j][1], c[j][1]);
+            qz = qz + __fmul_rn(c[j][2], c[j][2]);
+        }
+    }
+    for (; k < p.kn; ++k, src += stride) {
+        const float cx = src[0], cy = src[1], cz = src[2];
+        sx = sx + cx;
+        sy = sy + cy;
+        sz = sz + cz;
+        qx = qx + __fmul_rn(cx, cx);
+        qy = qy + __fmul_rn(cy, cy);
+        qz = qz + __fmul_rn(cz, cz);
+    }
+    s[0] = sx;
+    s[1] = sy;
+    s[2] = sz;
+    q[0] = qx;
+    q[1] = qy;
+    q[2] = qz;
+}
+
+// rtx_accum_resolve_device: the mean, the biased variance of the mean and the noisy-pixel count of an accumulator
+// after n samples, in float32 exactly as rtx.h states (no square root, no contraction).  Thread i reads slot i of the
+// tile-major S and Q and writes its pixel's row of the row-major outputs.  Every thread of a wave reaches the ballot —
+// a slot past the end or outside a ragged tile votes "not noisy" instead of returning — and the wave's first lane adds
+// the popcount with one global atomic.
+__global__ __launch_bounds__(256) void resolve_accum(ResolveArgs a) {
+    const uint32_t twl = a.tile_w_log2;
+    const uint32_t tiles_x = tiles_x_of(a.width, twl);
+    const size_t n_tiles = (size_t)tiles_x * tiles_y_of(a.rows, twl);
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const uint32_t t = (uint32_t)(i >> 6), l = (uint32_t)(i & 63u);
+    const uint32_t lx = ((t % tiles_x) << twl) + (l & ((1u << twl) - 1u)), lr = (t / tiles_x) * (64u >> twl) + (l >> twl);
+    const bool live = i < n_tiles * 64 && lx < a.width && lr < a.rows;
+    bool noisy = false;
+    if (live) {
+        const float* s = a.s + i * 3;
+        const float* q = a.q + i * 3;
+        const float inv = 1.0f / (float)a.n;
+        float m[3], v[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            m[c] = __fmul_rn(s[c], inv);
+            const float d = __fsub_rn(__fmul_rn(q[c], inv), __fmul_rn(m[c], m[c]));
+            v[c] = __fmul_rn(d > 0.0f ? d : 0.0f, inv);  // (a NaN compares false: 0)
+        }
+        const size_t o = ((size_t)lr * a.width + lx) * 3;
+        a.rgb[o] = m[0];
+        a.rgb[o + 1] = m[1];
+        a.rgb[o + 2] = m[2];
+        if (a.var) {
+            a.var[o] = v[0];
+            a.var[o + 1] = v[1];
+            a.var[o + 2] = v[2];
+        }
+        const float sv = __fadd_rn(__fadd_rn(v[0], v[1]), v[2]);
+        const float mb = __fadd_rn(__fadd_rn(m[0], m[1]), m[2]);
+        const float tol = __fmul_rn(a.rel_tol, mb > 0.01f ? mb : 0.01f);
+        noisy = sv > __fmul_rn(tol, tol);
+    }
+    if (a.noisy) {  // (uniform: a kernel argument)
+        const unsigned long long votes = __ballot(noisy);
+        if ((threadIdx.x & 63u) == 0u && votes) atomicAdd(a.noisy, (unsigned long long)__popcll(votes));
+    }
+}
+
+hipError_t launch_resolve(const ResolveArgs& a, hipStream_t stream) {
+    if (a.width == 0 || a.rows == 0) return hipSuccess;
+    const uint64_t slots = (uint64_t)tiles_x_of(a.width, a.tile_w_log2) * tiles_y_of(a.rows, a.tile_w_log2) * 64;
+    hipLaunchKernelGGL(resolve_accum, dim3((uint32_t)((slots + 255) / 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+// The chunk's reduction: reduce_samples into p.out (a one-shot render; `last` scales by 1/spp), or
+// accumulate_samples into an accumulator's S and Q.
+inline void launch_reduce(const Params& p, const SampleRange& rg, uint64_t slots, bool last, hipStream_t stream) {
+    const dim3 grid((uint32_t)((slots + 255) / 256));
+    if (rg.s)
+        hipLaunchKernelGGL(accumulate_samples, grid, dim3(256), 0, stream, p, rg.s, rg.q);
+    else
+        hipLaunchKernelGGL(reduce_samples, grid, dim3(256), 0, stream, p, (uint32_t)last);
+}
+
 // ------------------------------------------------------------------------------------
 // launches
 // ------------------------------------------------------------------------------------
@@ -876,7 +1000,7 @@ hipError_t resident_grid(const void* kern, int block, size_t shmem, int* per_cu,
 // POOL (a scene in the LDS copy, the timed kernel): the camera-ray pool after the scene copy (render_items<POOL>).
 template <bool COUNT, bool QUADS, bool NOISE, int WAVES = 8, int MINW = 0, bool CLK = false, bool POOL = false,
           bool ST = false>
-hipError_t launch_items(Params p, bool use_lds, hipStream_t stream) {
+hipError_t launch_items(Params p, bool use_lds, hipStream_t stream, const SampleRange& rg) {
     // a scene too big for LDS: its top levels (p.n_hot entries) cached in LDS when the
     // device layout stored them first (RTX_HOT_ENTRIES=0 turns that off)
     const bool hyb = !use_lds && p.n_hot > 0 && !NOISE;
@@ -891,12 +1015,14 @@ hipError_t launch_items(Params p, bool use_lds, hipStream_t stream) {
     int cus = 0, per_cu = 0;
     hipError_t e = resident_grid((const void*)kern, block, shmem, &per_cu, &cus);
     if (e != hipSuccess) return e;
-    const uint32_t spp = p.cam.samples_per_pixel, chunk = p.kn, sub = p.sub;
+    // the samples [rg.first, end) of this call: a whole render, or one pass of an accumulator
+    const uint64_t end = (uint64_t)rg.first + rg.count;
+    const uint32_t chunk = p.kn, sub = p.sub;
     const uint64_t tiles = (uint64_t)tiles_x_of(p.width, p.tile_w_log2) * tiles_y_of(p.rows, p.tile_w_log2);
     const uint64_t slots = tiles * 64;  // pixels of the tile-major scratch (ragged tiles padded)
-    for (uint32_t k0 = 0; k0 < spp; k0 += chunk) {
-        p.k0 = k0;
-        p.kn = spp - k0 < chunk ? spp - k0 : chunk;
+    for (uint64_t k0 = rg.first; k0 < end; k0 += chunk) {
+        p.k0 = (uint32_t)k0;  // absolute: the Philox key is k, the scratch index k - k0
+        p.kn = end - k0 < chunk ? (uint32_t)(end - k0) : chunk;
         if (sub == 0) p.sub = unit_samples(tiles, p.kn, WAVES, per_cu, cus);
         const uint64_t units = tiles * ((p.kn + p.sub - 1) / p.sub);
         uint64_t blocks = (uint64_t)per_cu * cus;
@@ -907,8 +1033,7 @@ hipError_t launch_items(Params p, bool use_lds, hipStream_t stream) {
         e = hipMemsetAsync(p.tile_counter, 0, sizeof(uint32_t), stream);  // (the watchdog flag: once per render)
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(block), shmem, stream, p);
-        hipLaunchKernelGGL(reduce_samples, dim3((uint32_t)((slots + 255) / 256)), dim3(256), 0, stream, p,
-                           (uint32_t)(k0 + p.kn >= spp));
+        launch_reduce(p, rg, slots, k0 + p.kn >= end, stream);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -931,7 +1056,7 @@ inline size_t items_shmem(const Params& p, bool use_lds, bool hyb) {
 // passes keep WAVES.
 template <bool COUNT, int WAVES, int MINW, bool CLK = false, bool USE_LDS = true, bool HYB = false, bool POOL = false,
           bool ST = false, bool QUADS = false, int WN = POOL ? RTX_POOL_WAVES : WAVES>
-hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream) {
+hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream, const SampleRange& rg) {
     constexpr int MN = POOL && MINW ? RTX_POOL_MINW : MINW;  // the near (and drain) kernel's waves per SIMD
     const auto kn = render_items<COUNT, USE_LDS, QUADS, false, WN, MN, HYB, CLK, 1, POOL, ST>;
     const auto kf = render_items<COUNT, USE_LDS, QUADS, false, WAVES, MINW, HYB, CLK, 2>;  // (rows from the records)
@@ -957,7 +1082,8 @@ hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream) {
     bool drain = CAN_DRAIN && pn.drain && pn.drain_count;
     if (drain && (e = resident_grid(kd, block_n, sd, &per_d, &cus)) != hipSuccess) return e;
     drain = drain && per_d >= per_n;
-    const uint32_t spp = pn.cam.samples_per_pixel, chunk = pn.kn, sub = pn.sub;
+    const uint64_t end = (uint64_t)rg.first + rg.count;  // (launch_items)
+    const uint32_t chunk = pn.kn, sub = pn.sub;
     const uint64_t tiles = (uint64_t)tiles_x_of(pn.width, pn.tile_w_log2) * tiles_y_of(pn.rows, pn.tile_w_log2);
     const uint64_t slots = tiles * 64;
     Params pr = pf;  // the redo pass: the far layout over the chunk's units, flagged samples only
@@ -965,9 +1091,9 @@ hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream) {
     // the far and redo passes' unit queue heads: words of their own, zeroed with the chunk's others (chunk_start)
     pf.tile_counter = pn.drain_count + DRAIN_WORDS - 2;
     pr.tile_counter = pn.drain_count + DRAIN_WORDS - 1;
-    for (uint32_t k0 = 0; k0 < spp; k0 += chunk) {
-        pn.k0 = pf.k0 = pr.k0 = k0;
-        pn.kn = pf.kn = pr.kn = spp - k0 < chunk ? spp - k0 : chunk;
+    for (uint64_t k0 = rg.first; k0 < end; k0 += chunk) {
+        pn.k0 = pf.k0 = pr.k0 = (uint32_t)k0;
+        pn.kn = pf.kn = pr.kn = end - k0 < chunk ? (uint32_t)(end - k0) : chunk;
         pn.sub = sub ? sub : unit_samples(tiles, pn.kn, WN, per_n, cus, true);
         pf.sub = pr.sub = pn.sub;
         const uint64_t units = tiles * ((pn.kn + pn.sub - 1) / pn.sub);
@@ -982,7 +1108,7 @@ hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream) {
         // that set any); with the drain each workgroup's region is the queue over the near grid (a region that fills
         // sends the rest to the redo pass)
         const bool drain_now = drain && 2 * bn + 2 <= DRAIN_WORDS;
-        hipLaunchKernelGGL(chunk_start, dim3(1), dim3(256), 0, stream, pn, (uint32_t)(k0 == 0));
+        hipLaunchKernelGGL(chunk_start, dim3(1), dim3(256), 0, stream, pn, (uint32_t)(k0 == rg.first));
         if (drain_now) {
             pn.drain_region = pf.drain_region = pn.defer_cap / (uint32_t)bn;
             if constexpr (CAN_DRAIN)
@@ -994,8 +1120,7 @@ hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream) {
         }
         hipLaunchKernelGGL(spill_redo_list, dim3((uint32_t)cus * 4), dim3(256), 0, stream, pn);
         hipLaunchKernelGGL(kr, dim3((uint32_t)br), dim3(block), sf, stream, pr);
-        hipLaunchKernelGGL(reduce_samples, dim3((uint32_t)((slots + 255) / 256)), dim3(256), 0, stream, pn,
-                           (uint32_t)(k0 + pn.kn >= spp));
+        launch_reduce(pn, rg, slots, k0 + pn.kn >= end, stream);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
@@ -1011,22 +1136,22 @@ hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream) {
 #endif
 
 template <bool COUNT, bool ST>
-hipError_t launch_items_for(const Params& p, bool use_lds, hipStream_t stream) {
-    if (p.has_noise) return p.n_quads ? launch_items<COUNT, true, true, 8, 0, false, false, ST>(p, use_lds, stream)
-                                      : launch_items<COUNT, false, true, 8, 0, false, false, ST>(p, use_lds, stream);
+hipError_t launch_items_for(const Params& p, bool use_lds, hipStream_t stream, const SampleRange& rg) {
+    if (p.has_noise) return p.n_quads ? launch_items<COUNT, true, true, 8, 0, false, false, ST>(p, use_lds, stream, rg)
+                                      : launch_items<COUNT, false, true, 8, 0, false, false, ST>(p, use_lds, stream, rg);
     if (p.item_waves == 4)  // A/B: 4 waves per LDS copy of the scene
-        return p.n_quads ? launch_items<COUNT, true, false, 4, 0, false, false, ST>(p, use_lds, stream)
-                         : launch_items<COUNT, false, false, 4, 0, false, false, ST>(p, use_lds, stream);
+        return p.n_quads ? launch_items<COUNT, true, false, 4, 0, false, false, ST>(p, use_lds, stream, rg)
+                         : launch_items<COUNT, false, false, 4, 0, false, false, ST>(p, use_lds, stream, rg);
     // 6 waves per SIMD: at most 80 VGPRs (the allocation granule is 8)
     constexpr int MV = COUNT ? 0 : RTX_V3_MINW, MH = COUNT ? 0 : RTX_HYB_MINW, MP = COUNT ? 0 : RTX_POOL_MINW;
     if (!use_lds && p.n_hot > HOT_ENTRIES_8W)  // an LDS cache past a third of the CU: 12-wave workgroups, two per CU
-        return p.n_quads ? launch_items<COUNT, true, false, RTX_HYB_WAVES, MH, false, false, ST>(p, use_lds, stream)
-                         : launch_items<COUNT, false, false, RTX_HYB_WAVES, MH, false, false, ST>(p, use_lds, stream);
+        return p.n_quads ? launch_items<COUNT, true, false, RTX_HYB_WAVES, MH, false, false, ST>(p, use_lds, stream, rg)
+                         : launch_items<COUNT, false, false, RTX_HYB_WAVES, MH, false, false, ST>(p, use_lds, stream, rg);
     if (use_lds && pool_fits(p))  // the camera-ray pool (12-wave workgroups, two per CU) when the scene copy leaves room
-        return p.n_quads ? launch_items<COUNT, true, false, RTX_POOL_WAVES, MP, false, true, ST>(p, use_lds, stream)
-                         : launch_items<COUNT, false, false, RTX_POOL_WAVES, MP, false, true, ST>(p, use_lds, stream);
-    return p.n_quads ? launch_items<COUNT, true, false, RTX_V3_WAVES, MV, false, false, ST>(p, use_lds, stream)
-                     : launch_items<COUNT, false, false, RTX_V3_WAVES, MV, false, false, ST>(p, use_lds, stream);
+        return p.n_quads ? launch_items<COUNT, true, false, RTX_POOL_WAVES, MP, false, true, ST>(p, use_lds, stream, rg)
+                         : launch_items<COUNT, false, false, RTX_POOL_WAVES, MP, false, true, ST>(p, use_lds, stream, rg);
+    return p.n_quads ? launch_items<COUNT, true, false, RTX_V3_WAVES, MV, false, false, ST>(p, use_lds, stream, rg)
+                     : launch_items<COUNT, false, false, RTX_V3_WAVES, MV, false, false, ST>(p, use_lds, stream, rg);
 }
 
 uint32_t scene_placement(const Params& p, uint32_t flags) {
@@ -1045,7 +1170,7 @@ uint32_t tier_placement(const Params& near, const Params& far, uint32_t flags) {
 
 // ST: the render's shard is striped (Params::stripe_log2 > 0): every kernel's ST instantiation (render_items).
 template <bool ST>
-hipError_t launch_render_t(const Params& p, uint32_t flags, hipStream_t stream, const Params* far) {
+hipError_t launch_render_t(const Params& p, uint32_t flags, hipStream_t stream, const Params* far, const SampleRange& rg) {
     const bool count = (flags & RTX_FLAG_COUNTERS) != 0;
     if (far) {  // the caller checked: spheres only, both layouts placed alike (tier_placement), no noise
         const uint32_t place = tier_placement(p, *far, flags);
@@ -1057,46 +1182,49 @@ hipError_t launch_render_t(const Params& p, uint32_t flags, hipStream_t stream, 
                 constexpr int V = RTX_V3_WAVES, MV = RTX_V3_MINW, H = RTX_HYB_WAVES, MH = RTX_HYB_MINW;
                 if (place == RTX_SCENE_IN_LDS) {
                     const bool pool = pool_fits(p);
-                    if (count) return pool ? launch_tiered<true, V, 0, false, true, false, true, false, true>(p, *far, stream)
-                                           : launch_tiered<true, V, 0, false, true, false, false, false, true>(p, *far, stream);
-                    return pool ? launch_tiered<false, V, MV, false, true, false, true, false, true>(p, *far, stream)
-                                : launch_tiered<false, V, MV, false, true, false, false, false, true>(p, *far, stream);
+                    if (count) return pool ? launch_tiered<true, V, 0, false, true, false, true, false, true>(p, *far, stream, rg)
+                                           : launch_tiered<true, V, 0, false, true, false, false, false, true>(p, *far, stream, rg);
+                    return pool ? launch_tiered<false, V, MV, false, true, false, true, false, true>(p, *far, stream, rg)
+                                : launch_tiered<false, V, MV, false, true, false, false, false, true>(p, *far, stream, rg);
                 }
                 if (place == RTX_SCENE_LDS_CACHE)
-                    return count ? launch_tiered<true, H, 0, false, false, true, false, false, true>(p, *far, stream)
-                                 : launch_tiered<false, H, MH, false, false, true, false, false, true>(p, *far, stream);
-                return count ? launch_tiered<true, V, 0, false, false, false, false, false, true>(p, *far, stream)
-                             : launch_tiered<false, V, MV, false, false, false, false, false, true>(p, *far, stream);
+                    return count ? launch_tiered<true, H, 0, false, false, true, false, false, true>(p, *far, stream, rg)
+                                 : launch_tiered<false, H, MH, false, false, true, false, false, true>(p, *far, stream, rg);
+                return count ? launch_tiered<true, V, 0, false, false, false, false, false, true>(p, *far, stream, rg)
+                             : launch_tiered<false, V, MV, false, false, false, false, false, true>(p, *far, stream, rg);
             }
         }
         const bool clk = !count && (flags & RTX_FLAG_TIMING);  // diagnostics: the wave-cycle split of the passes
         constexpr int V = RTX_V3_WAVES, MV = RTX_V3_MINW, H = RTX_HYB_WAVES, MH = RTX_HYB_MINW;
         if (place == RTX_SCENE_IN_LDS) {
             const bool pool = pool_fits(p);  // (the counting kernel too: its schedule counters are the timed kernel's)
-            if (clk) return pool ? launch_tiered<false, V, MV, true, true, false, true, ST>(p, *far, stream)
-                                 : launch_tiered<false, V, MV, true, true, false, false, ST>(p, *far, stream);
-            if (count) return pool ? launch_tiered<true, V, 0, false, true, false, true, ST>(p, *far, stream)
-                                   : launch_tiered<true, V, 0, false, true, false, false, ST>(p, *far, stream);
-            return pool ? launch_tiered<false, V, MV, false, true, false, true, ST>(p, *far, stream)
-                        : launch_tiered<false, V, MV, false, true, false, false, ST>(p, *far, stream);
+            if (clk) return pool ? launch_tiered<false, V, MV, true, true, false, true, ST>(p, *far, stream, rg)
+                                 : launch_tiered<false, V, MV, true, true, false, false, ST>(p, *far, stream, rg);
+            if (count) return pool ? launch_tiered<true, V, 0, false, true, false, true, ST>(p, *far, stream, rg)
+                                   : launch_tiered<true, V, 0, false, true, false, false, ST>(p, *far, stream, rg);
+            return pool ? launch_tiered<false, V, MV, false, true, false, true, ST>(p, *far, stream, rg)
+                        : launch_tiered<false, V, MV, false, true, false, false, ST>(p, *far, stream, rg);
         }
         if (place == RTX_SCENE_LDS_CACHE)  // both cached in LDS (tier_placement): 12-wave workgroups, two per CU
-            return count ? launch_tiered<true, H, 0, false, false, true, false, ST>(p, *far, stream)
-                         : launch_tiered<false, H, MH, false, false, true, false, ST>(p, *far, stream);
-        return count ? launch_tiered<true, V, 0, false, false, false, false, ST>(p, *far, stream)
-                     : launch_tiered<false, V, MV, false, false, false, false, ST>(p, *far, stream);
+            return count ? launch_tiered<true, H, 0, false, false, true, false, ST>(p, *far, stream, rg)
+                         : launch_tiered<false, H, MH, false, false, true, false, ST>(p, *far, stream, rg);
+        return count ? launch_tiered<true, V, 0, false, false, false, false, ST>(p, *far, stream, rg)
+                     : launch_tiered<false, V, MV, false, false, false, false, ST>(p, *far, stream, rg);
     }
     const bool use_lds = scene_placement(p, flags) == RTX_SCENE_IN_LDS;
     if (!count && (flags & RTX_FLAG_TIMING) && !p.has_noise && p.item_waves != 4)  // diagnostics: sphere scenes
-        return p.n_quads ? launch_items<false, true, false, RTX_V3_WAVES, RTX_V3_MINW, true, false, ST>(p, use_lds, stream)
-                         : launch_items<false, false, false, RTX_V3_WAVES, RTX_V3_MINW, true, false, ST>(p, use_lds, stream);
-    return count ? launch_items_for<true, ST>(p, use_lds, stream) : launch_items_for<false, ST>(p, use_lds, stream);
+        return p.n_quads ? launch_items<false, true, false, RTX_V3_WAVES, RTX_V3_MINW, true, false, ST>(p, use_lds, stream, rg)
+                         : launch_items<false, false, false, RTX_V3_WAVES, RTX_V3_MINW, true, false, ST>(p, use_lds, stream, rg);
+    return count ? launch_items_for<true, ST>(p, use_lds, stream, rg) : launch_items_for<false, ST>(p, use_lds, stream, rg);
 }
 
-hipError_t launch_render(const Params& p, uint32_t flags, hipStream_t stream, const Params* far) {
+hipError_t launch_render(const Params& p, uint32_t flags, hipStream_t stream, const Params* far, const SampleRange* pass) {
     if (p.width == 0 || p.rows == 0) return hipSuccess;
     if (!p.scratch) return hipErrorInvalidValue;  // the caller sizes the sample scratch
-    return p.stripe_log2 ? launch_render_t<true>(p, flags, stream, far) : launch_render_t<false>(p, flags, stream, far);
+    if (pass && (!pass->s || !pass->q || pass->count == 0 || pass->first + pass->count < pass->first))
+        return hipErrorInvalidValue;
+    const SampleRange rg = pass ? *pass : SampleRange{0u, p.cam.samples_per_pixel, nullptr, nullptr};
+    return p.stripe_log2 ? launch_render_t<true>(p, flags, stream, far, rg) : launch_render_t<false>(p, flags, stream, far, rg);
 }
 
 }  // namespace rtxd

@@ -127,6 +127,9 @@ RTX_SYMBOLS = [
     "rtx_camera_octant", "rtx_walk_tree", "rtx_render_ex", "rtx_scene_walk_skip", "rtx_walk_skip",
     "rtx_scene_near_region", "rtx_scene_near_skip", "rtx_walk_near_region", "rtx_render_ppm_ex", "rtx_region_row",
     "rtx_device_check",
+    # progressive rendering (ABI 10, additive)
+    "rtx_accum_create", "rtx_accum_add", "rtx_accum_samples", "rtx_accum_resolve_device", "rtx_accum_resolve",
+    "rtx_accum_ppm", "rtx_accum_reset", "rtx_accum_destroy",
 ]
 RTXHOST_SYMBOLS = [
     "rtxhost_build_scene", "rtxhost_scene_free", "rtxhost_scene_desc", "rtxhost_scene_camera",
@@ -222,6 +225,23 @@ def load() -> ctypes.CDLL:
     if hasattr(L, "rtx_device_check"):  # ABI 10 (RTX_LIB may name an older build for A/B)
         L.rtx_device_check.argtypes = [c_int]
         L.rtx_device_check.restype = c_int
+    if hasattr(L, "rtx_accum_create"):  # ABI 10, additive (RTX_LIB may name an older build for A/B)
+        L.rtx_accum_create.argtypes = [c_void_p, POINTER(Camera), c_uint64, POINTER(Region), POINTER(c_void_p)]
+        L.rtx_accum_create.restype = c_int
+        L.rtx_accum_add.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, POINTER(Stats)]
+        L.rtx_accum_add.restype = c_int
+        L.rtx_accum_samples.argtypes = [c_void_p]
+        L.rtx_accum_samples.restype = c_uint32
+        L.rtx_accum_resolve_device.argtypes = [c_void_p, c_void_p, c_void_p, c_float, c_void_p, POINTER(c_uint64)]
+        L.rtx_accum_resolve_device.restype = c_int
+        L.rtx_accum_resolve.argtypes = [c_void_p, c_void_p, c_void_p, c_float, POINTER(c_uint64)]
+        L.rtx_accum_resolve.restype = c_int
+        L.rtx_accum_ppm.argtypes = [c_void_p, c_void_p, c_uint64, POINTER(c_uint64)]
+        L.rtx_accum_ppm.restype = c_int
+        L.rtx_accum_reset.argtypes = [c_void_p]
+        L.rtx_accum_reset.restype = c_int
+        L.rtx_accum_destroy.argtypes = [c_void_p]
+        L.rtx_accum_destroy.restype = None
     _lib = L
     return L
 
@@ -469,9 +489,83 @@ class DeviceScene:
         out = buf[: n.value].tobytes()
         return (out, st) if stats else out
 
+    def accumulator(self, cam: Camera, seed: int, region: Region) -> "Accumulator":
+        """rtx_accum_create on the current device: progressive passes over `region` (close it before the scene)."""
+        return Accumulator(self, cam, seed, region)
+
     def close(self) -> None:
         if self._h:
             load().rtx_scene_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Accumulator:
+    """rtx_accum: sample passes over one (scene, device, camera, seed, region) that can be resolved in between.
+    After n samples resolve() is bit-identical to a one-shot render with samples_per_pixel = n.  The caller orders
+    the passes and resolves of one accumulator (the same stream, or a synchronise between)."""
+
+    def __init__(self, scene: DeviceScene, cam: Camera, seed: int, region: Region):
+        h = c_void_p()
+        check(load().rtx_accum_create(scene.handle, ctypes.byref(cam), seed, ctypes.byref(region), ctypes.byref(h)),
+              "rtx_accum_create")
+        self._h = h
+        self._scene = scene  # destroyed after the accumulator
+        self.width = region.width
+        self.rows = region_rows(region)
+
+    def add(self, count: int, stream: int = 0, stats: bool = False, counters: bool = False, flags: int = 0):
+        """One pass of `count` samples per pixel; returns the pass's Stats (after waiting) when asked for."""
+        st = Stats() if (stats or counters) else None
+        check(load().rtx_accum_add(self._h, count, c_void_p(stream), flags | (RTX_FLAG_COUNTERS if counters else 0),
+                                   ctypes.byref(st) if st is not None else None), "rtx_accum_add")
+        return st
+
+    @property
+    def samples(self) -> int:
+        return int(load().rtx_accum_samples(self._h))
+
+    def resolve_device(self, rgb_ptr: int, var_ptr: int = 0, rel_tol: float = 0.0, stream: int = 0,
+                       count_noisy: bool = False):
+        """rtx_accum_resolve_device into device memory; returns the noisy-pixel count (after waiting) when
+        count_noisy, else None (enqueued only)."""
+        n = c_uint64()
+        check(load().rtx_accum_resolve_device(self._h, c_void_p(rgb_ptr), c_void_p(var_ptr) if var_ptr else None,
+                                              rel_tol, c_void_p(stream), ctypes.byref(n) if count_noisy else None),
+              "rtx_accum_resolve_device")
+        return int(n.value) if count_noisy else None
+
+    def resolve(self, rel_tol: float = 0.0):
+        """(rgb, var, noisy): float32 [rows, width, 3] host arrays and the noisy-pixel count at rel_tol."""
+        import numpy as np
+        rgb = np.zeros((self.rows, self.width, 3), dtype=np.float32)
+        var = np.zeros_like(rgb)
+        n = c_uint64()
+        check(load().rtx_accum_resolve(self._h, rgb.ctypes.data_as(c_void_p), var.ctypes.data_as(c_void_p), rel_tol,
+                                       ctypes.byref(n)), "rtx_accum_resolve")
+        return rgb, var, int(n.value)
+
+    def ppm(self) -> bytes:
+        """rtx_accum_ppm: the P3 bytes of the image so far."""
+        import numpy as np
+        L = load()
+        cap = int(L.rtx_ppm_max_bytes(self.width, self.rows))
+        buf = np.empty(cap, dtype=np.uint8)
+        n = c_uint64()
+        check(L.rtx_accum_ppm(self._h, buf.ctypes.data_as(c_void_p), cap, ctypes.byref(n)), "rtx_accum_ppm")
+        return buf[: n.value].tobytes()
+
+    def reset(self) -> None:
+        check(load().rtx_accum_reset(self._h), "rtx_accum_reset")
+
+    def close(self) -> None:
+        if self._h:
+            load().rtx_accum_destroy(self._h)
             self._h = None
 
     def __del__(self):
