@@ -511,6 +511,10 @@ constexpr uint32_t DRAIN_WORDS = 16384;  // Params::drain_count's words: near gr
 // The camera-ray pool of render_items<POOL>: after the fixed layout's scene copy (16-B aligned), 64 rays
 // of 2 float4 per wave (2 KB).
 constexpr uint32_t POOL_BYTES_PER_WAVE = 64 * 32;
+// The last word of a pool entry is its item's global pixel, y * image_width + x (the RNG's counter word), or this
+// for a lane outside a ragged tile.  No pixel has it: rtx_capi refuses an image of more than 2^32 - 1 pixels
+// (check_camera: image_width * image_height <= 0xFFFFFFFF), so every index is at most 2^32 - 2.
+constexpr uint32_t POOL_NO_ITEM = 0xFFFFFFFFu;
 #ifndef RTX_POOL_WAVES  // waves per workgroup of the pooled kernels (two workgroups per CU) and their waves per SIMD
 #define RTX_POOL_WAVES 12
 #define RTX_POOL_MINW 6
@@ -569,21 +573,16 @@ struct Counters {
 // does not count draws may leave its rejection loop out (Cornell box -1.7 %).
 // b = block (0, 0) of the sample, drawn by the caller (the shading phase draws it together with
 // the other lanes' scatter blocks: one Philox evaluation for both).
-template <bool SKIP_DISK = false>
-__device__ __forceinline__ Ray camera_ray(const rtx_camera& c, V3 base, const PathRng& rng, U4 b, uint32_t& draws) {
+// In three steps, so that the camera-ray pool's block fill can resolve the disk sample for the whole wave between
+// the first and the last (coop_disk, rtx_kernel.hip): the sampled pixel centre, the disk's rejection loop, the ray.
+__device__ __forceinline__ V3 camera_pixel_centre(const rtx_camera& c, V3 base, U4 b) {
     const V3 du = v3(c.pixel_du[0], c.pixel_du[1], c.pixel_du[2]);
     const V3 dv = v3(c.pixel_dv[0], c.pixel_dv[1], c.pixel_dv[2]);
     const float dx = -0.5f + unit_f32(b.x);                       // :290
     const float dy = -0.5f + unit_f32(b.y);                       // :291
-    const V3 pc = add(base, add(scale(du, dx), scale(dv, dy)));   // :275
-    float x = signed_unit(b.z), y = signed_unit(b.w);             // :277 disk, always drawn
-    draws += 4;
-    for (uint32_t a = 1; !(SKIP_DISK && !(c.defocus_angle > 0.0f)) && !(x * x + y * y < 1.0f); ++a) {  // vec3.go:203-210
-        b = rng.block(0, a);
-        x = signed_unit(b.x);
-        y = signed_unit(b.y);
-        draws += 2;
-    }
+    return add(base, add(scale(du, dx), scale(dv, dy)));          // :275
+}
+__device__ __forceinline__ Ray camera_ray_from(const rtx_camera& c, V3 pc, float x, float y) {  // (x, y): the disk sample
     const V3 center = v3(c.center[0], c.center[1], c.center[2]);
     V3 origin = center;
     if (c.defocus_angle > 0.0f) {                                 // :279-281
@@ -592,6 +591,19 @@ __device__ __forceinline__ Ray camera_ray(const rtx_camera& c, V3 base, const Pa
         origin = add(center, add(scale(ddu, x), scale(ddv, y)));
     }
     return Ray{origin, sub(pc, origin)};                          // :283-286
+}
+template <bool SKIP_DISK = false>
+__device__ __forceinline__ Ray camera_ray(const rtx_camera& c, V3 base, const PathRng& rng, U4 b, uint32_t& draws) {
+    const V3 pc = camera_pixel_centre(c, base, b);
+    float x = signed_unit(b.z), y = signed_unit(b.w);             // :277 disk, always drawn
+    draws += 4;
+    for (uint32_t a = 1; !(SKIP_DISK && !(c.defocus_angle > 0.0f)) && !(x * x + y * y < 1.0f); ++a) {  // vec3.go:203-210
+        b = rng.block(0, a);
+        x = signed_unit(b.x);
+        y = signed_unit(b.y);
+        draws += 2;
+    }
+    return camera_ray_from(c, pc, x, y);
 }
 
 __device__ __forceinline__ V3 pixel_base(const rtx_camera& c, uint32_t x, uint32_t y) {  // camera.go:266-274
@@ -654,6 +666,44 @@ __device__ __forceinline__ uint32_t hit_material(const SceneRef E, uint32_t hit)
     return RTX_DEV_SPHERE_MATERIAL(__float_as_int(b.w));
 }
 
+// One round of a wave-cooperative rejection loop (coop_scatter, coop_disk): the np lanes still rejecting (`pend`)
+// get K = 64 / np consecutive lanes each.  Lane i evaluates attempt base + k of lane `owner` when `slot`; an owner
+// (`mine`, the below-th pending lane) then finds its K results at bits below * K .. of the round's ballot.
+struct CoopRound {
+    uint32_t K, below, k, owner;
+    bool mine, slot;
+};
+__device__ __forceinline__ CoopRound coop_round(uint64_t pend, uint32_t lane, uint64_t below_mask) {
+    const uint32_t np = (uint32_t)__popcll(pend);
+    // K = 64 / np attempts per owner this round, and q = lane / K below, by float reciprocals:
+    // 64.5 / np and (lane + 0.5) / K lie at least 1/128 from the next integer, far beyond
+    // v_rcp_f32's 1-ulp error, so truncation gives the integer quotients (the compiler's
+    // integer divisions took ~25 VALU per round).
+    const uint32_t K = __builtin_amdgcn_readfirstlane((uint32_t)(64.5f * __builtin_amdgcn_rcpf((float)np)));
+    const bool mine = (pend >> lane) & 1ull;
+    const uint32_t below = (uint32_t)__popcll(pend & below_mask);
+    // Lane q (< np) learns the lane id of the q-th pending lane (a permutation push).
+    const uint32_t dst = mine ? below : np + (lane - below);
+    const uint32_t owner_of = (uint32_t)__builtin_amdgcn_ds_permute((int)(dst * 4u), (int)lane);
+    const uint32_t q = (uint32_t)(((float)lane + 0.5f) * __builtin_amdgcn_rcpf((float)K)), k = lane - q * K;
+    const bool slot = q < np;
+    const uint32_t owner = lane_pull(slot ? q : 0u, owner_of);
+    return CoopRound{K, below, k, owner, mine, slot};
+}
+// The owner's FIRST accepted attempt of the round, given the ballot `good` of the slots that accepted: attempt
+// base + kk, evaluated by lane src (a lane that is no owner, or found none: src = itself, found = false).
+struct CoopPick {
+    uint32_t kk, src;
+    bool found;
+};
+__device__ __forceinline__ CoopPick coop_pick(const CoopRound& r, uint64_t good, uint32_t lane) {
+    const uint64_t kmask = r.K >= 64u ? ~0ull : ((1ull << r.K) - 1ull);
+    const uint64_t mine_good = r.mine ? ((good >> (r.below * r.K)) & kmask) : 0ull;
+    const uint32_t kk = mine_good ? (uint32_t)__builtin_ctzll(mine_good) : 0u;
+    const uint32_t src = mine_good ? r.below * r.K + kk : lane;
+    return CoopPick{kk, src, mine_good != 0ull};
+}
+
 // Wave-cooperative rejection sampling for NewVec3UnitRandOnUnitSphere32 (vec3.go:182-190).
 // Must be called by the whole wave (converged).  A lane with hit >= 0 draws block (e, 0);
 // its words 0-2 are attempt 0 of the unit-sphere loop.  The loop's result is the FIRST
@@ -686,46 +736,61 @@ __device__ __forceinline__ Scatter coop_scatter(const Params& p, const SceneRef 
     const uint32_t lane = __lane_id();
     const uint64_t below_mask = (1ull << lane) - 1ull;
     for (uint32_t base = 1; pend != 0;) {
-        const uint32_t np = (uint32_t)__popcll(pend);
-        // K = 64 / np attempts per owner this round, and q = lane / K below, by float reciprocals:
-        // 64.5 / np and (lane + 0.5) / K lie at least 1/128 from the next integer, far beyond
-        // v_rcp_f32's 1-ulp error, so truncation gives the integer quotients (the compiler's
-        // integer divisions took ~25 VALU per round).
-        const uint32_t K = __builtin_amdgcn_readfirstlane((uint32_t)(64.5f * __builtin_amdgcn_rcpf((float)np)));
-        const bool mine = (pend >> lane) & 1ull;
-        const uint32_t below = (uint32_t)__popcll(pend & below_mask);
-        // Lane q (< np) learns the lane id of the q-th pending lane (a permutation push).
-        const uint32_t dst = mine ? below : np + (lane - below);
-        const uint32_t owner_of = (uint32_t)__builtin_amdgcn_ds_permute((int)(dst * 4u), (int)lane);
-        const uint32_t q = (uint32_t)(((float)lane + 0.5f) * __builtin_amdgcn_rcpf((float)K)), k = lane - q * K;
-        const bool slot = q < np;
-        const uint32_t owner = lane_pull(slot ? q : 0u, owner_of);
-        const uint32_t opix = lane_pull(owner, rng.pixel), osmp = lane_pull(owner, rng.sample);
-        const uint32_t oe = lane_pull(owner, e);
-        const U4 b = philox4x32_10(opix, osmp, oe, base + k, rng.k0, rng.k1);
+        const CoopRound cr = coop_round(pend, lane, below_mask);
+        const uint32_t opix = lane_pull(cr.owner, rng.pixel), osmp = lane_pull(cr.owner, rng.sample);
+        const uint32_t oe = lane_pull(cr.owner, e);
+        const U4 b = philox4x32_10(opix, osmp, oe, base + cr.k, rng.k0, rng.k1);
         const float bx = signed_unit(b.x), by = signed_unit(b.y), bz = signed_unit(b.z);
-        const uint64_t good = ballot(slot) & ballot(bx * bx + by * by + bz * bz < 1.0f);
-        const uint64_t kmask = K >= 64u ? ~0ull : ((1ull << K) - 1ull);
-        const uint64_t mine_good = mine ? ((good >> (below * K)) & kmask) : 0ull;
-        const uint32_t kk = mine_good ? (uint32_t)__builtin_ctzll(mine_good) : 0u;
-        const uint32_t src = mine_good ? below * K + kk : lane;
-        const float fx = __int_as_float((int)lane_pull(src, __float_as_uint(bx)));
-        const float fy = __int_as_float((int)lane_pull(src, __float_as_uint(by)));
-        const float fz = __int_as_float((int)lane_pull(src, __float_as_uint(bz)));
-        if (mine_good) {
+        const uint64_t good = ballot(cr.slot) & ballot(bx * bx + by * by + bz * bz < 1.0f);
+        const CoopPick pk = coop_pick(cr, good, lane);
+        const float fx = __int_as_float((int)lane_pull(pk.src, __float_as_uint(bx)));
+        const float fy = __int_as_float((int)lane_pull(pk.src, __float_as_uint(by)));
+        const float fz = __int_as_float((int)lane_pull(pk.src, __float_as_uint(bz)));
+        if (pk.found) {
             x = fx;
             y = fy;
             z = fz;
-            att = base + kk;
+            att = base + pk.kk;
         }
-        pend &= ~ballot(mine_good != 0ull);  // (ballot(mine) is pend)
-        base += K;
+        pend &= ~ballot(pk.found);  // (ballot(mine) is pend)
+        base += cr.K;
     }
     if (need) {
         out.s = unit(v3(x, y, z));
         out.draws = 3u * (att + 1u);
     }
     return out;
+}
+
+// The same for NewVec3UnitRandInUnitDisk32 (vec3.go:203-210) at the camera-ray pool's block fill (rtx_kernel.hip):
+// 64 camera rays of ONE sample (cr.sample wave-uniform, cr.pixel the lane's global pixel), event 0.  Attempt 0 is
+// words 2, 3 of block (0, 0), which the caller drew and tested: `pending` = inside the image and rejected (a lane
+// outside a ragged tile owns nothing and votes false).  Attempt a >= 1 is words 0, 1 of block (0, a).  Acceptance
+// pi/4: ~14 of 64 lanes pending, so 4 attempts per owner in the first round; (x, y) and att change only for the
+// lanes that were pending, each to its FIRST accepted attempt — what the lane's own loop (camera_ray) finds.
+// A round pulls one value, the owner's pixel (coop_scatter: pixel, sample and event).
+// Must be called by the whole wave (converged), as coop_scatter.
+__device__ __forceinline__ void coop_disk(const PathRng& cr, bool pending, float& x, float& y, uint32_t& att) {
+    uint64_t pend = ballot(pending);
+    const uint32_t lane = __lane_id();
+    const uint64_t below_mask = (1ull << lane) - 1ull;
+    for (uint32_t base = 1; pend != 0;) {
+        const CoopRound rd = coop_round(pend, lane, below_mask);
+        const uint32_t opix = lane_pull(rd.owner, cr.pixel);
+        const U4 b = philox4x32_10(opix, cr.sample, 0u, base + rd.k, cr.k0, cr.k1);
+        const float bx = signed_unit(b.x), by = signed_unit(b.y);
+        const uint64_t good = ballot(rd.slot) & ballot(bx * bx + by * by < 1.0f);
+        const CoopPick pk = coop_pick(rd, good, lane);
+        const float fx = __int_as_float((int)lane_pull(pk.src, __float_as_uint(bx)));
+        const float fy = __int_as_float((int)lane_pull(pk.src, __float_as_uint(by)));
+        if (pk.found) {
+            x = fx;
+            y = fy;
+            att = base + pk.kk;
+        }
+        pend &= ~ballot(pk.found);
+        base += rd.K;
+    }
 }
 
 // One step of the closest-hit walk over the threaded pre-order layout (rtx_layout.h):

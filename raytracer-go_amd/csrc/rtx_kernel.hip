@@ -570,6 +570,13 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
                     }
                 }
             }
+            if constexpr (POOL) {
+                // the block fill below draws for the whole wave (coop_disk): none without it, as at the unit claim
+                if (!exhausted && (cursor >> 6) != pool_blk && partial_wave()) {
+                    RTX_SET_KERR();
+                    exhausted = true;
+                }
+            }
             if (exhausted) {
                 if (mode == M_CLAIM) mode = M_DONE;
                 break;
@@ -577,18 +584,33 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
             uint32_t avail = u_items - cursor;  // items this round can hand out
             if constexpr (POOL) {
                 const uint32_t blk = cursor >> 6;
-                if (blk != pool_blk) {  // the block's 64 camera rays, one per lane (sample u_k0 + blk, pixel lane)
+                // The block's 64 camera rays, one per lane (sample u_k0 + blk, pixel lane).  Wave-uniform (cursor and
+                // pool_blk are) and run by the whole wave: every lane of the wave is in this loop, whose exits are
+                // uniform, and the guard above stops a wave that is not whole.
+                if (blk != pool_blk) {
                     pool_blk = blk;
                     const rtx_camera& c = RTX_KARG_CAM ? karg_params().cam : p.cam;
                     const uint32_t lx = u_x + (lane & tw_mask), lr = u_r + (lane >> twl);
-                    if (lx < p.width && lr < p.rows) {
+                    const bool in = lx < p.width && lr < p.rows;  // else: a lane outside a ragged tile, which owns no item
+                    PathRng cr{rng.k0, rng.k1, POOL_NO_ITEM, u_k0 + blk};
+                    V3 pc = v3(0.0f, 0.0f, 0.0f);
+                    float dkx = 0.0f, dky = 0.0f;  // the disk sample: attempt 0 is words 2, 3 of block (0, 0)
+                    if (in) {
                         const uint32_t x = p.x0 + lx, y = ST ? u_y + (lane >> twl) : p.y0 + p.rank + lr * p.world;
-                        const PathRng cr{rng.k0, rng.k1, y * c.image_width + x, u_k0 + blk};
-                        uint32_t dr = 0;
-                        const Ray cray = camera_ray<!COUNT>(c, pixel_base(c, x, y), cr, cr.block(0u, 0u), dr);
-                        pool[2 * lane] = make_float4(cray.o.x, cray.o.y, cray.o.z, __uint_as_float(dr));  // (COUNT: draws)
-                        pool[2 * lane + 1] = make_float4(cray.d.x, cray.d.y, cray.d.z, 0.0f);
+                        cr.pixel = y * c.image_width + x;
+                        const U4 b = cr.block(0u, 0u);
+                        pc = camera_pixel_centre(c, pixel_base(c, x, y), b);
+                        dkx = signed_unit(b.z);
+                        dky = signed_unit(b.w);
                     }
+                    // the rejection loop where camera_ray<!COUNT> runs it: defocus on, or the counting kernel
+                    uint32_t att = 0;
+                    if (COUNT || c.defocus_angle > 0.0f) coop_disk(cr, in && !(dkx * dkx + dky * dky < 1.0f), dkx, dky, att);
+                    const Ray cray = camera_ray_from(c, pc, dkx, dky);
+                    // o.w: the ray's draws (COUNT); d.w: the item's global pixel, which its claiming lane takes as it is,
+                    // or POOL_NO_ITEM
+                    pool[2 * lane] = make_float4(cray.o.x, cray.o.y, cray.o.z, __uint_as_float(4u + 2u * att));
+                    pool[2 * lane + 1] = make_float4(cray.d.x, cray.d.y, cray.d.z, __uint_as_float(cr.pixel));
                     __builtin_amdgcn_wave_barrier();  // (LDS is in order within the wave)
                 }
                 avail = min(u_items, 64u * blk + 64u) - cursor;
@@ -608,6 +630,22 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
                 pix = __float_as_uint(q3.w);
                 mode = M_START;
                 ready = true;
+            } else if (POOL) {
+                // The item the wave drew for (l: the pixel of the block): its ray and its global pixel, as the fill left
+                // them.  Every lane reads an entry (any lane's l is within the pool) and the claiming lanes keep theirs:
+                // one test and one LDS round trip, not a read of the marker before the reads of the ray.  The round's
+                // items lie in one block (avail), so their sample is the block's.
+                const uint32_t l = (cursor + rank) & 63u;  // sample-major within the unit
+                const float4 po = pool[2 * l], pd = pool[2 * l + 1];
+                // else: outside a ragged tile, claim again
+                got = mode == M_CLAIM && rank < avail && __float_as_uint(pd.w) != POOL_NO_ITEM;
+                if (got) {
+                    r = Ray{v3(po.x, po.y, po.z), v3(pd.x, pd.y, pd.z)};
+                    if (COUNT) pool_draws = __float_as_uint(po.w);
+                    rng.pixel = __float_as_uint(pd.w);
+                    rng.sample = u_k0 + (cursor >> 6);
+                    pix = 64u * u_tile + l;
+                }
             } else if (TIER != 2 && mode == M_CLAIM && rank < avail) {
                 uint32_t j = cursor + rank, l = j & 63u;  // sample-major within the unit
                 uint32_t lx = u_x + (l & tw_mask);
@@ -631,13 +669,7 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
                                    y = !ST ? p.y0 + p.rank + lr * p.world
                                            : (TIER == 3 && listed ? p.y0 + region_row(lr, p.rank, p.world, p.stripe_log2)
                                                                   : u_y + (l >> twl));
-                    if constexpr (POOL) {  // the ray the wave drew for this item (l: the pixel of the block)
-                        const float4 po = pool[2 * l], pd = pool[2 * l + 1];
-                        r = Ray{v3(po.x, po.y, po.z), v3(pd.x, pd.y, pd.z)};
-                        if (COUNT) pool_draws = __float_as_uint(po.w);
-                    } else {
-                        base = pixel_base(c, x, y);
-                    }
+                    base = pixel_base(c, x, y);
                     rng.pixel = y * c.image_width + x;
                     rng.sample = k;
                     pix = (uint32_t)slot;

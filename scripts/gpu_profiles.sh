@@ -2,12 +2,14 @@
 # gpurun: PMC profiles of every bench workload on this library — the configs of SURVEY §8(d),
 # the Cornell box, and rank 0's rows of the 2/4/8-GPU headline runs (bench.py --shard 0/N) — then the
 # bench line of each, whose roofline.frac derives from them.  Per workload three rocprofv3 passes of one
-# timed render (bench.py --steps 1 --warmup 0): VALU + wave-state counters, FETCH_SIZE, WRITE_SIZE.
+# timed render (bench.py --steps 1 --warmup 0): VALU + wave-state counters, FETCH_SIZE, WRITE_SIZE; counter passes
+# only, no tracing flag beside --pmc (the kernel trace is a run of its own: scripts/gpu_final_a.sh).
 # Summaries append to gpurun_out/$TAG/{valu,traffic}_r05.jsonl, copied into profiles/ on the box.
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 R=${ROUND:-06}; TAG=${TAG:-prof$R}; OUT="$PWD/gpurun_out/$TAG"; mkdir -p "$OUT"; export TMPDIR=/tmp
-PV="SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
+# (PV: the VALU pass; SQ_ACTIVE_INST_VALU is pmc_valu.py's valu_busy.  A set too large for one pass fails the pass: PV overrides.)
+PV=${PV:-"SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_ACTIVE_INST_VALU"}
 declare -a NAMES ARGS KEYS
 add() { NAMES+=("$1"); KEYS+=("$2"); ARGS+=("$3"); }
 add c2 "random_spheres:1920x1080x500" ""
@@ -29,7 +31,7 @@ for i in "${!NAMES[@]}"; do
   cmd="python bench.py --steps 1 --warmup 0 --no-cpu --no-hash --no-verify $a"; mkdir -p "$OUT/$n"
   for pass in valu fetch write; do
     case $pass in valu) P="$PV";; fetch) P="FETCH_SIZE";; write) P="WRITE_SIZE";; esac
-    timeout -s KILL 300 rocprofv3 --kernel-trace --pmc $P -d "$OUT/$n/$pass" -o run --output-format csv -- $cmd \
+    timeout -s KILL 300 rocprofv3 --pmc $P -d "$OUT/$n/$pass" -o run --output-format csv -- $cmd \
         > "$OUT/$n/$pass.log" 2>&1 || { rc=$?; echo "$n $pass failed rc=$rc"; break 2; }
   done
   python scripts/pmc_valu.py "$OUT/$n/valu" "$OUT/valu_r$R.jsonl" --workload "$k" --renders 1 > "$OUT/$n/valu.json" && \

@@ -56,11 +56,18 @@ out = {
     "shader_cycles_per_launch": cycles,
     "valu_issue_frac": round(insts * 2.0 / (cycles * args.simds), 4),
     "valu_lane_frac": round(thread_cycles / (64.0 * insts), 4),
+    # SQ_ACTIVE_INST_VALU per SIMD-cycle, as the counter comes (no unit applied), and per VALU instruction.  On gfx950
+    # it came out at 1.01 per instruction: a count that follows the instructions, not their cycles, so
+    # it does not say how busy the VALU is.  None when the pass did not collect the counter.
+    "valu_busy": (round(vals["SQ_ACTIVE_INST_VALU"] / renders["SQ_INSTS_VALU"] / (cycles * args.simds), 4)
+                  if "SQ_ACTIVE_INST_VALU" in vals else None),
+    "valu_active_per_inst": (round(vals["SQ_ACTIVE_INST_VALU"] / vals["SQ_INSTS_VALU"], 4)
+                             if "SQ_ACTIVE_INST_VALU" in vals else None),
     "kernels": sorted({k for (f, c, k) in disp}),
     "librtx_sha256_16": hashlib.sha256(open(args.lib, "rb").read()).hexdigest()[:16],
     # every counter of the pass per launch (SQ_INSTS_SALU, SQ_WAIT_ANY, SQ_WAVE_CYCLES, ... when collected)
     "counters_per_launch": {c: v / (args.renders or renders["SQ_INSTS_VALU"]) for c, v in sorted(vals.items())},
-    "method": "rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU GRBM_GUI_ACTIVE ...; "
+    "method": "rocprofv3 --pmc SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU GRBM_GUI_ACTIVE ... (no tracing beside it); "
               "issue frac = 2 cycles x SQ_INSTS_VALU / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs)",
 }
 if args.out.endswith(".jsonl"):  # one line per (workload, library): replace this one's, keep the others
