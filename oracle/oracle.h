@@ -15,6 +15,13 @@
  * published Random123 known-answer vectors), plus known-answer tests derived from the
  * source text (tests/test_oracle_kat.py).
  *
+ * Second opinion: tests/ref64.py reads the same Go source again, independently of this file
+ * (numpy, float64 and float32, no BVH, its own Philox); tests/test_ref64.py holds this oracle
+ * to it, and tests/test_ref64_gpu.py the kernel, on every sample whose decisions do not hang
+ * on float32 rounding.  That pins the reading of Sphere.Hit, Quad.Hit,
+ * NewHitInfo, the UV and texture lookups, the materials, GetRay and the draw order.  It does
+ * not pin the Go binary itself, nor the bits of Go's libm (ref64 uses numpy's).
+ *
  * Every function cites the reference file:line it restates.  Float semantics: IEEE
  * float32, no contraction (built with -ffp-contract=off), float64 exactly where the Go
  * code widens to float64.
