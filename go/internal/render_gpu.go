@@ -128,6 +128,10 @@ type gpuTables struct {
 	listRefs  []C.int32_t
 	matIdx    map[Material]C.uint32_t
 	texIdx    map[Texture]C.uint32_t
+	// the Go values behind the table indices, for HitBatch: rtx_hit.prim and .material back to what was flattened
+	sphereOf   []*Sphere
+	quadOf     []Quad
+	materialOf []Material
 }
 
 // errUnsupported: a scene part the GPU path does not carry (RenderGPU then uses Render).
@@ -233,6 +237,7 @@ func (t *gpuTables) material(m Material) (C.uint32_t, error) {
 	}
 	i := C.uint32_t(len(t.materials))
 	t.materials = append(t.materials, r)
+	t.materialOf = append(t.materialOf, m)
 	t.matIdx[m] = i
 	return i, nil
 }
@@ -266,6 +271,7 @@ func (t *gpuTables) ref(h Hittable) (C.int32_t, error) {
 			return 0, err
 		}
 		t.spheres = append(t.spheres, C.rtx_sphere{center: vec(v.Center), radius: C.float(v.Radius), material: mi})
+		t.sphereOf = append(t.sphereOf, v)
 		return primRef(C.RTX_PRIM_SPHERE, len(t.spheres)-1), nil
 	case Quad, *Quad: // fields as NewQuad derived them (hittables.go:149-165)
 		q, ok := v.(Quad)
@@ -279,6 +285,7 @@ func (t *gpuTables) ref(h Hittable) (C.int32_t, error) {
 		t.quads = append(t.quads, C.rtx_quad{
 			q: vec(q.Q), material: mi, u: vec(q.u), d: C.float(q.D), v: vec(q.v), w: vec(q.w), normal: vec(q.normal),
 		})
+		t.quadOf = append(t.quadOf, q)
 		return primRef(C.RTX_PRIM_QUAD, len(t.quads)-1), nil
 	case *World: // a World nested in the tree (hittables.go:55-72 as a BVH child): a list ref
 		// (an empty one is a miss: a list of no items, ABI 6)
@@ -374,6 +381,12 @@ func (c *Camera) RenderGPU(world Hittable, writer io.Writer, seed uint64, gpus i
 // NewBVHFromWorldGPU tree): the caller destroys the scene.  Go slices stay pinned only for the
 // call; librtx copies them and keeps no pointer into Go memory.
 func sceneOf(world Hittable, seed uint64) (*C.rtx_scene, error) {
+	scene, _, err := sceneTables(world, seed)
+	return scene, err
+}
+
+// sceneTables is sceneOf that also returns the flattened tables (HitBatch maps hits back through them).
+func sceneTables(world Hittable, seed uint64) (*C.rtx_scene, *gpuTables, error) {
 	var pin runtime.Pinner
 	defer pin.Unpin()
 	var scene *C.rtx_scene
@@ -382,16 +395,17 @@ func sceneOf(world Hittable, seed uint64) (*C.rtx_scene, error) {
 		for _, h := range g.world.hittables { // spheres in Add order: NewBVH's input list
 			s, ok := h.(*Sphere)
 			if !ok {
-				return nil, errFallback
+				return nil, nil, errFallback
 			}
 			mi, err := t.material(s.Material)
 			if err != nil {
-				return nil, err
+				return nil, nil, err
 			}
 			t.spheres = append(t.spheres, C.rtx_sphere{center: vec(s.Center), radius: C.float(s.Radius), material: mi})
+			t.sphereOf = append(t.sphereOf, s)
 		}
 		if len(t.spheres) == 0 {
-			return nil, errFallback
+			return nil, nil, errFallback
 		}
 		pin.Pin(&t.spheres[0])
 		pin.Pin(&t.materials[0])
@@ -408,13 +422,13 @@ func sceneOf(world Hittable, seed uint64) (*C.rtx_scene, error) {
 		if rc := C.rtx_scene_create_spheres(&t.spheres[0], C.uint32_t(len(t.spheres)), &t.materials[0],
 			C.uint32_t(len(t.materials)), tex, C.uint32_t(len(t.textures)), texels, C.uint64_t(len(t.texels)),
 			C.uint64_t(seed), 0, &scene, nil); rc != 0 {
-			return nil, rtxErr(rc)
+			return nil, nil, rtxErr(rc)
 		}
-		return scene, nil
+		return scene, t, nil
 	}
 	t, err := flatten(world)
 	if err != nil {
-		return nil, err
+		return nil, nil, err
 	}
 	var desc C.rtx_scene_desc
 	if len(t.nodes) > 0 {
@@ -450,9 +464,78 @@ func sceneOf(world Hittable, seed uint64) (*C.rtx_scene, error) {
 		desc.list_refs, desc.n_list_refs = &t.listRefs[0], C.uint32_t(len(t.listRefs))
 	}
 	if rc := C.rtx_scene_create(&desc, &scene); rc != 0 {
-		return nil, rtxErr(rc)
+		return nil, nil, rtxErr(rc)
 	}
-	return scene, nil
+	return scene, t, nil
+}
+
+// HitBatch is Hittable.Hit (hittables.go:7-20) for a batch of rays on the GPU: hits[i], ok[i] are what
+// world.Hit(&rays[i], rayT[i]) returns (rtx_trace, rtx.h "ray queries": the closest hit with the ray's own
+// interval, ties as the reference's walk resolves them).  The world is flattened and uploaded for the call
+// (sceneOf) and rtx_hit.prim / .material are mapped back to the Go values that were flattened: the hit's
+// Material is the primitive's own.  u and v are filled (RTX_TRACE_UV).  A world the GPU path does not carry
+// returns errFallback; the caller then loops over world.Hit.
+func HitBatch(world Hittable, rays []Ray, rayT []Interval) ([]HitInfo, []bool, error) {
+	if len(rays) != len(rayT) {
+		return nil, nil, errors.New("rtx: HitBatch needs one interval per ray")
+	}
+	infos, oks := make([]HitInfo, len(rays)), make([]bool, len(rays))
+	if len(rays) == 0 {
+		return infos, oks, nil
+	}
+	scene, t, err := sceneTables(world, 0)
+	if errors.Is(err, errUnsupported) {
+		return nil, nil, errFallback
+	}
+	if err != nil {
+		return nil, nil, err
+	}
+	defer C.rtx_scene_destroy(scene)
+	// rtx_trace wants both tables 16-B aligned, which a Go slice of a 4-B aligned struct does not promise: byte
+	// slices with room to start on a 16-B boundary, pinned for the call (they hold no Go pointers)
+	aligned := func(bytes uintptr) ([]byte, unsafe.Pointer) {
+		buf := make([]byte, bytes+16)
+		off := (16 - uintptr(unsafe.Pointer(&buf[0]))%16) % 16
+		return buf, unsafe.Pointer(&buf[off])
+	}
+	inBuf, inPtr := aligned(uintptr(len(rays)) * unsafe.Sizeof(C.rtx_ray{}))
+	outBuf, outPtr := aligned(uintptr(len(rays)) * unsafe.Sizeof(C.rtx_hit{}))
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pin.Pin(&inBuf[0])
+	pin.Pin(&outBuf[0])
+	in, out := (*C.rtx_ray)(inPtr), (*C.rtx_hit)(outPtr)
+	cin, cout := unsafe.Slice(in, len(rays)), unsafe.Slice(out, len(rays))
+	for i := range rays {
+		cin[i] = C.rtx_ray{origin: vec(rays[i].origin), tmin: C.float(rayT[i].min), dir: vec(rays[i].dir), tmax: C.float(rayT[i].max)}
+	}
+	if rc := C.rtx_trace(scene, in, C.uint64_t(len(rays)), out, C.RTX_TRACE_UV, nil); rc != 0 {
+		if gpuMissing(rc) {
+			return nil, nil, errFallback
+		}
+		return nil, nil, rtxErr(rc)
+	}
+	v3 := func(a [3]C.float) Vec3 { return NewVec3(float32(a[0]), float32(a[1]), float32(a[2])) }
+	for i := range cout {
+		var rec C.rtx_hit = cout[i]
+		if rec.prim == C.RTX_HIT_NONE {
+			continue
+		}
+		var mat Material
+		switch idx := int(rec.prim & 0x0FFFFFFF); rec.prim >> 28 {
+		case C.RTX_PRIM_SPHERE:
+			mat = t.sphereOf[idx].Material
+		case C.RTX_PRIM_QUAD:
+			mat = t.quadOf[idx].material
+		}
+		if mat == nil { // (cannot happen: prim names a flattened primitive)
+			mat = t.materialOf[int(rec.material)]
+		}
+		infos[i] = HitInfo{point: v3(rec.point), normal: v3(rec.normal), t: float32(rec.t), u: float32(rec.u),
+			v: float32(rec.v), material: mat, frontFace: rec.front_face != 0}
+		oks[i] = true
+	}
+	return infos, oks, nil
 }
 
 // gpuCamera is Camera.init's derived state (camera.go:128-165) as rtx.h's kernel constants.

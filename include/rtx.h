@@ -567,6 +567,79 @@ int rtx_accum_reset(rtx_accum* accum);
 /* Frees the accumulator's device memory (NULL is a no-op).  Blocking. */
 void rtx_accum_destroy(rtx_accum* accum);
 
+/* ---- ray queries (ABI 10, additive) ------------------------------
+ * The question under Render, the reference's own public interface:
+ *   Hittable.Hit(r *Ray, rayT Interval) (HitInfo, bool)          hittables.go:7-20, bvh.go:220-249
+ * for a batch of the CALLER's rays against the world handed to rtx_scene_create*: picking, auto-focus,
+ * shadow and occlusion rays, first-hit guide images, an integrator written elsewhere.
+ *
+ * Closest hit.  Hit i is what world.Hit(ray_i, Interval{tmin, tmax}) returns:
+ *  - the running bound starts at tmax; Interval.In is strict at both ends (bvh.go:18-20), so a root equal
+ *    to tmin or tmax is no hit; Aabb.Hit gets (tmin, running bound) (bvh.go:52-61, 84-102);
+ *  - equal roots are resolved as the reference's walk resolves them, whichever tree is walked (the
+ *    render's rank rule): of two spheres with the same root, the one the reference's walk
+ *    meets first;
+ *  - tmin >= tmax is a miss, and so is a NaN tmin or tmax (every comparison with it is false);
+ *  - NaN, infinite and zero origin and direction components are legal and take the IEEE forms of the Go
+ *    code (1 / 0 = inf, 0 * inf = NaN fails `t0 > min`), as in a render.
+ * `prim` names the caller's table index whichever tree was walked; `material` indexes
+ * rtx_scene_desc.materials.  point = r.At(t) (ray.go:25-30); normal is unit and flipped against the ray,
+ * front_face says whether it had to be (NewHitInfo, hittables.go:22-37).  A miss: t = +inf,
+ * prim = RTX_HIT_NONE, every other field 0.
+ * RTX_TRACE_ANY: each ray stops at the first primitive it accepts (a shadow ray); only
+ * prim != RTX_HIT_NONE is specified, and it holds for exactly the rays whose closest hit exists (the two
+ * walks take the same steps with the same bound, tmax, up to the first accepted primitive).
+ * n == 0 returns RTX_OK and launches nothing.  A NULL scene, ray or hit pointer, a ray or hit pointer
+ * not aligned to 16 B, flag bits other than those below, and (rtx_trace_device) a current device that
+ * holds no copy of the scene return RTX_ERR_INVALID_ARG.
+ * A trace takes the scene's mutex like a render.  It uses none of the per-device sample scratch
+ * (rtx_device_scratch_bytes is unchanged by it, rtx_release_device_memory does not disturb it), walks
+ * layouts of its own (a render's walk, and so its node_visits, is what it is without the trace) and
+ * keeps its counters in memory of its own: a counting trace between two renders changes neither's stats. */
+typedef struct rtx_ray { /* 32 B */
+    float origin[3];
+    float tmin;
+    float dir[3]; /* any length: t is in units of it, as in the reference */
+    float tmax;
+} rtx_ray;
+typedef struct rtx_hit { /* 48 B */
+    float t;             /* HitInfo.t; +inf on a miss                                        */
+    uint32_t prim;       /* type << 28 | index into the CALLER's sphere / quad table (RTX_PRIM_*);
+                            RTX_HIT_NONE on a miss                                           */
+    uint32_t material;   /* index into rtx_scene_desc.materials                              */
+    uint32_t front_face; /* 1: the ray came from outside (dot(dir, outward normal) < 0)      */
+    float point[3];      /* r.At(t), ray.go:25-30                                            */
+    float u;
+    float normal[3];     /* unit, flipped against the ray: NewHitInfo, hittables.go:22-37    */
+    float v;
+} rtx_hit;
+#define RTX_HIT_NONE 0xFFFFFFFFu
+#define RTX_TRACE_ANY 1u      /* stop at the lane's first accepted primitive; only prim != RTX_HIT_NONE is specified */
+#define RTX_TRACE_UV 2u       /* fill u, v (sphere: hittables.go:122-126; quad: alpha, beta); else 0 */
+#define RTX_TRACE_COUNTERS 4u /* counting instantiation: hits, node_visits, prim_tests (with stats only) */
+/* hint: the direction signs (rtx_camera_octant's bits) the tree's child order should suit; a scene that
+ * walks its own trees (rtx_scene_create_ex) has one per octant.  Every hint gives the same hits. */
+#define RTX_TRACE_OCTANT(o) (((uint32_t)(o)&7u) << 8)
+typedef struct rtx_trace_stats {
+    uint64_t rays;
+    uint64_t hits;            /* RTX_TRACE_COUNTERS: rays with a hit                                  */
+    uint64_t node_visits;     /* RTX_TRACE_COUNTERS: AABB slab tests (bvh.go:221), as rtx_stats'      */
+    uint64_t prim_tests;      /* RTX_TRACE_COUNTERS: ray-primitive tests, as rtx_stats'               */
+    uint64_t walk_layout;     /* the hinted octant of a rebuilt tree, or RTX_LAYOUT_REFERENCE         */
+    uint64_t scene_placement; /* RTX_SCENE_IN_LDS or RTX_SCENE_IN_HBM                                 */
+    double kernel_ms;         /* device time of the launches, HIP events on the stream                */
+} rtx_trace_stats;
+
+/* Rays and hits in device memory of the CURRENT device, on the given HIP stream (hipStream_t, NULL =
+ * default stream).  Returns after enqueueing unless stats != NULL; then it synchronises the stream and
+ * fills stats.  The trace layout and the rank table are uploaded on the first trace that needs them
+ * (blocking copies).  n beyond what one launch indexes in 32 bits is cut into several launches. */
+int rtx_trace_device(rtx_scene* scene, const rtx_ray* d_rays, uint64_t n, rtx_hit* d_hits, uint32_t flags,
+                     void* hip_stream, rtx_trace_stats* stats);
+/* The same for rays and hits in host memory, on the current device.  Blocking. */
+int rtx_trace(rtx_scene* scene, const rtx_ray* rays, uint64_t n, rtx_hit* hits, uint32_t flags,
+              rtx_trace_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -889,8 +889,7 @@ __device__ __forceinline__ void load_entry(const SceneRef E, uint32_t pos, float
 // (Quad).Hit, hittables.go:167-194, of the quad entry (ea, eb) at `pos` against (tmin, closest).
 template <bool COUNT>
 __device__ __forceinline__ void quad_test(Trav& t, const Ray& r, const SceneRef E, const float4 ea, const float4 eb,
-                                          uint32_t pos, Counters& cnt) {
-    const float tmin = 0.001f;  // ray.go:37
+                                          uint32_t pos, Counters& cnt, const float tmin = 0.001f) {  // ray.go:37
     if (COUNT) ++cnt.prim_tests;
     const float denom = r.d.x * ea.x + r.d.y * ea.y + r.d.z * ea.z;                 // :168
     if (!(__builtin_fabs((double)denom) < 1e-8)) {                                   // :170
@@ -923,7 +922,9 @@ __device__ __forceinline__ float div_by(float n, float a, float y) {
 }
 
 // (*Sphere).Hit, hittables.go:96-116, of the sphere entry (ea, eb) at `pos` against (tmin, closest).
-// SAFE: the two divisions by a as div_by.
+// tmin (here, in quad_test and in box_hit): a render's 0.001 (ray.go:37) by default, a constant that folds
+// into every render kernel as before; the ray queries (rtx_trace.hip) pass each ray's own.
+// SAFE: the two divisions by a as div_by (needs tmin >= 2^-126: an accepted quotient is then normal).
 // RANKED (the LDS layout, whose primitives are stored in the reference walk's order): a root equal
 // to `closest` also wins when the sphere comes before the current hit in the reference's order —
 // the tie bvh.go:220-249 resolves for the sphere it meets first (the right subtree is clipped to the
@@ -934,8 +935,8 @@ __device__ __forceinline__ float div_by(float n, float a, float y) {
 // hit's read from bt = the 'b' halves — only on an exact tie.
 template <bool COUNT, bool SAFE = false, bool RANKED = false, bool RANK_WORD = false>
 __device__ __forceinline__ void sphere_test(Trav& t, const Ray& r, const float4 ea, const float4 eb, uint32_t pos,
-                                            Counters& cnt, const float4* __restrict__ bt = nullptr) {
-    const float tmin = 0.001f;  // ray.go:37
+                                            Counters& cnt, const float4* __restrict__ bt = nullptr,
+                                            const float tmin = 0.001f) {  // ray.go:37
     if (COUNT) ++cnt.prim_tests;
     const float ox = r.o.x - ea.x, oy = r.o.y - ea.y, oz = r.o.z - ea.z;  // :97
     const float hb = r.d.x * ox + r.d.y * oy + r.d.z * oz;                 // :99
@@ -1065,8 +1066,7 @@ __device__ __forceinline__ bool quad_own_box_pass(const Trav& t, const Ray& r, c
 // only when every walking lane's ray is safe, which for the near pass includes near_fma_ok).
 template <bool MED3 = false, bool FMA = false>
 __device__ __forceinline__ bool box_hit(const Trav& t, const Ray& r, const float4 ea, const float4 eb,
-                                        const V3 no = V3{0.0f, 0.0f, 0.0f}) {
-    const float tmin = 0.001f;  // ray.go:37
+                                        const V3 no = V3{0.0f, 0.0f, 0.0f}, const float tmin = 0.001f) {  // ray.go:37
     if constexpr (MED3) {
         float tax, tbx, tay, tby, taz, tbz;
         if constexpr (FMA) {
@@ -1113,11 +1113,11 @@ __device__ __forceinline__ bool box_hit(const Trav& t, const Ray& r, const float
 
 template <bool COUNT, bool MED3 = false, bool FMA = false>
 __device__ __forceinline__ void box_step(Trav& t, const Ray& r, const float4 ea, const float4 eb, int32_t tag,
-                                         Counters& cnt, const V3 no = V3{0.0f, 0.0f, 0.0f}) {
+                                         Counters& cnt, const V3 no = V3{0.0f, 0.0f, 0.0f}, const float tmin = 0.001f) {
     if (COUNT && __float_as_int(ea.w) != tag) ++cnt.node_visits;  // (not the sentinel: escape == next)
     // the next entry on a box hit, else the escape (both stored as walk positions): a
     // mask select (a ?: here became a branch).
-    const uint32_t take = 0u - (uint32_t)box_hit<MED3, FMA>(t, r, ea, eb, no);
+    const uint32_t take = 0u - (uint32_t)box_hit<MED3, FMA>(t, r, ea, eb, no, tmin);
     t.i = ((uint32_t)tag & take) | ((uint32_t)__float_as_int(ea.w) & ~take);
 }
 
@@ -1157,7 +1157,7 @@ __device__ __forceinline__ void trav_step(Trav& t, const Ray& r, const SceneRef 
 template <bool COUNT, bool QUADS, bool FIXED, bool HYB, bool MED3, bool FMA = false>
 __device__ __forceinline__ uint32_t trav_step_batched(Trav& t, const Ray& r, const SceneRef E, Counters& cnt,
                                                       uint32_t end, uint32_t kmin, uint32_t& idle,
-                                                      const V3 no = V3{0.0f, 0.0f, 0.0f}) {
+                                                      const V3 no = V3{0.0f, 0.0f, 0.0f}, const float tmin = 0.001f) {
     float4 ea, eb;
     load_entry<FIXED, HYB>(E, t.i, ea, eb);
     const int32_t tag = __float_as_int(eb.w);
@@ -1170,13 +1170,13 @@ __device__ __forceinline__ uint32_t trav_step_batched(Trav& t, const Ray& r, con
     if (prims) {
         if (__builtin_amdgcn_inverse_ballot_w64(pm)) {  // = prim, as the vote's mask (no second compare)
             if (COUNT && HYB && t.i < E.hot) ++cnt.cache_hits;
-            if (QUADS && tag == RTX_E_QUAD) quad_test<COUNT>(t, r, E, ea, eb, t.i, cnt);
-            else sphere_test<COUNT, MED3, FIXED, !FIXED>(t, r, ea, eb, t.i, cnt, E.b);
+            if (QUADS && tag == RTX_E_QUAD) quad_test<COUNT>(t, r, E, ea, eb, t.i, cnt, tmin);
+            else sphere_test<COUNT, MED3, FIXED, !FIXED>(t, r, ea, eb, t.i, cnt, E.b, tmin);
             t.i = (uint32_t)__float_as_int(eb.z);
         }
     } else if (__builtin_amdgcn_inverse_ballot_w64(bm)) {  // lanes on a node (the sentinel's step is a no-op)
         if (COUNT && HYB && t.i < E.hot) ++cnt.cache_hits;
-        box_step<COUNT, MED3, FMA>(t, r, ea, eb, tag, cnt, no);
+        box_step<COUNT, MED3, FMA>(t, r, ea, eb, tag, cnt, no, tmin);
     }
     if (COUNT) {
         const uint32_t walking = (uint32_t)__popcll(pm | bm);

@@ -38,6 +38,16 @@ RTX_TREE_NEAR = 0x100  # rtx_scene_topology / rtx_walk_tree octant bit: the near
 RTX_GATHER_NONE, RTX_GATHER_RCCL, RTX_GATHER_DEVICE, RTX_GATHER_HOST = 0, 1, 2, 3  # Stats.gather_kind
 RTX_SCENE_IN_HBM, RTX_SCENE_IN_LDS, RTX_SCENE_LDS_CACHE = 0, 1, 2  # Stats.scene_placement
 RTX_IMAGE_TEXEL_WORDS = 2  # RGBA16 image texels: two uint32 words each (rtx.h)
+# ray queries (rtx_trace*, ABI 10 additive)
+RTX_HIT_NONE = 0xFFFFFFFF  # Hit.prim of a miss
+RTX_TRACE_ANY = 1  # stop at the first accepted primitive: only prim != RTX_HIT_NONE is specified
+RTX_TRACE_UV = 2  # fill u, v
+RTX_TRACE_COUNTERS = 4  # the counting instantiation (with stats)
+
+
+def RTX_TRACE_OCTANT(o: int) -> int:
+    """Hint: the direction signs (camera_octant's bits) the walked tree's child order should suit."""
+    return (o & 7) << 8
 
 
 def RTX_FLAG_SHADE_THRESH(n: int) -> int:
@@ -119,6 +129,36 @@ class Stats(ctypes.Structure):
                 for name, _ in self._fields_}
 
 
+class TraceRay(ctypes.Structure):  # rtx_ray, 32 B
+    _fields_ = [("origin", c_float * 3), ("tmin", c_float), ("dir", c_float * 3), ("tmax", c_float)]
+
+
+class TraceHit(ctypes.Structure):  # rtx_hit, 48 B
+    _fields_ = [("t", c_float), ("prim", c_uint32), ("material", c_uint32), ("front_face", c_uint32),
+                ("point", c_float * 3), ("u", c_float), ("normal", c_float * 3), ("v", c_float)]
+
+
+class TraceStats(ctypes.Structure):  # rtx_trace_stats
+    _fields_ = [("rays", c_uint64), ("hits", c_uint64), ("node_visits", c_uint64), ("prim_tests", c_uint64),
+                ("walk_layout", c_uint64), ("scene_placement", c_uint64), ("kernel_ms", c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+def __getattr__(name: str):
+    """RAY_DTYPE / HIT_DTYPE: the numpy structured dtypes of rtx_ray and rtx_hit (numpy is imported on first use,
+    as everywhere in this module)."""
+    if name in ("RAY_DTYPE", "HIT_DTYPE"):
+        import numpy as np
+        ray = np.dtype([("origin", "<f4", (3,)), ("tmin", "<f4"), ("dir", "<f4", (3,)), ("tmax", "<f4")])
+        hit = np.dtype([("t", "<f4"), ("prim", "<u4"), ("material", "<u4"), ("front_face", "<u4"),
+                        ("point", "<f4", (3,)), ("u", "<f4"), ("normal", "<f4", (3,)), ("v", "<f4")])
+        globals().update(RAY_DTYPE=ray, HIT_DTYPE=hit)
+        return globals()[name]
+    raise AttributeError(f"module 'rtx' has no attribute {name!r}")
+
+
 RTX_SYMBOLS = [
     "rtx_version", "rtx_build_info", "rtx_last_error", "rtx_device_count", "rtx_scene_create",
     "rtx_scene_destroy", "rtx_scene_device_bytes", "rtx_render", "rtx_render_region_device", "rtx_region_rows",
@@ -130,6 +170,8 @@ RTX_SYMBOLS = [
     # progressive rendering (ABI 10, additive)
     "rtx_accum_create", "rtx_accum_add", "rtx_accum_samples", "rtx_accum_resolve_device", "rtx_accum_resolve",
     "rtx_accum_ppm", "rtx_accum_reset", "rtx_accum_destroy",
+    # ray queries (ABI 10, additive)
+    "rtx_trace_device", "rtx_trace",
 ]
 RTXHOST_SYMBOLS = [
     "rtxhost_build_scene", "rtxhost_scene_free", "rtxhost_scene_desc", "rtxhost_scene_camera",
@@ -242,6 +284,11 @@ def load() -> ctypes.CDLL:
         L.rtx_accum_reset.restype = c_int
         L.rtx_accum_destroy.argtypes = [c_void_p]
         L.rtx_accum_destroy.restype = None
+    if hasattr(L, "rtx_trace_device"):  # ABI 10, additive (RTX_LIB may name an older build for A/B)
+        L.rtx_trace_device.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, POINTER(TraceStats)]
+        L.rtx_trace_device.restype = c_int
+        L.rtx_trace.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(TraceStats)]
+        L.rtx_trace.restype = c_int
     _lib = L
     return L
 
@@ -489,6 +536,34 @@ class DeviceScene:
         out = buf[: n.value].tobytes()
         return (out, st) if stats else out
 
+    def trace_device(self, rays_ptr: int, n: int, hits_ptr: int, flags: int = 0, stream: int = 0, stats: bool = False):
+        """rtx_trace_device: n rtx_ray at rays_ptr -> n rtx_hit at hits_ptr, device memory of the current device
+        (16-B aligned: a torch tensor's data_ptr()).  Enqueues and returns None, or with stats=True waits and returns
+        the TraceStats (flags | RTX_TRACE_COUNTERS fills its work counters)."""
+        st = TraceStats() if stats else None
+        check(load().rtx_trace_device(self._h, c_void_p(rays_ptr), n, c_void_p(hits_ptr), flags, c_void_p(stream),
+                                      ctypes.byref(st) if st is not None else None), "rtx_trace_device")
+        return st
+
+    def trace(self, rays, flags: int = 0, stats: bool = False):
+        """rtx_trace: a numpy array of RAY_DTYPE in, an array of HIT_DTYPE of the same shape out (and the TraceStats
+        with stats=True).  Blocking."""
+        import numpy as np
+        ray_t, hit_t = __getattr__("RAY_DTYPE"), __getattr__("HIT_DTYPE")
+        rays = np.asarray(rays)
+        if rays.dtype != ray_t:
+            raise TypeError(f"rays must have dtype rtx.RAY_DTYPE, not {rays.dtype}")
+        n = rays.size
+        # 16-B aligned copies: numpy aligns a structured array to its widest field only (4 B)
+        src = _aligned_empty(n, ray_t)
+        src[...] = rays.reshape(-1)
+        out = _aligned_empty(n, hit_t)
+        st = TraceStats() if stats else None
+        check(load().rtx_trace(self._h, src.ctypes.data_as(c_void_p), n, out.ctypes.data_as(c_void_p), flags,
+                               ctypes.byref(st) if st is not None else None), "rtx_trace")
+        out = out.reshape(rays.shape)
+        return (out, st) if stats else out
+
     def accumulator(self, cam: Camera, seed: int, region: Region) -> "Accumulator":
         """rtx_accum_create on the current device: progressive passes over `region` (close it before the scene)."""
         return Accumulator(self, cam, seed, region)
@@ -573,6 +648,14 @@ class Accumulator:
             self.close()
         except Exception:
             pass
+
+
+def _aligned_empty(n: int, dtype):
+    """n records of a structured dtype starting on a 16-B boundary (rtx_trace's rule), uninitialised."""
+    import numpy as np
+    raw = np.empty(n * dtype.itemsize + 16, np.uint8)
+    off = (-raw.ctypes.data) % 16
+    return raw[off: off + n * dtype.itemsize].view(dtype)
 
 
 def release_device_memory(device: int = -1) -> None:
