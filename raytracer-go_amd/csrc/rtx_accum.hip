@@ -1,0 +1,194 @@
+// rtx_accum.hip — progressive rendering (ABI 10, additive).
+#include <algorithm>
+#include <new>
+
+#include "rtx_internal.h"
+#include "rtx_ppm.h"
+
+using namespace rtxh;
+
+// One (scene, device, camera, seed, region): the running sums S and Q of its shard's sample colours, tile-major
+// (rtx_kernel.hip accumulate_samples), owned by the accumulator and not part of the per-device scratch, and the
+// samples done.
+struct rtx_accum {
+    rtx_scene* scene = nullptr;
+    int device = -1;
+    rtx_camera cam;
+    uint64_t seed = 0;
+    rtx_region region;
+    uint32_t rows = 0;         // region_rows(&region)
+    uint32_t tile_w_log2 = 0;  // the tiles S and Q are laid out in (make_params)
+    uint64_t slots = 0;        // tiles x 64
+    rtxd::DeviceBuffer sums;   // S: slots x 3 floats, then Q's slots x 3
+    rtxd::DeviceBuffer noisy;  // resolve_accum's count (one u64)
+    uint32_t n = 0;
+    float* s() const { return sums.as<float>(); }
+    float* q() const { return s() + slots * 3; }
+};
+
+namespace {
+// The accumulator's device is the current one (every entry that touches its memory).
+int accum_device(const rtx_accum* a) {
+    int cur = 0;
+    HIP_TRY(hipGetDevice(&cur));
+    if (cur != a->device)
+        return fail(RTX_ERR_INVALID_ARG, "the accumulator lives on device %d, the current device is %d", a->device, cur);
+    return RTX_OK;
+}
+size_t accum_bytes(const rtx_accum* a) { return (size_t)a->slots * 3 * sizeof(float); }  // of S, and of Q
+
+// rtx_accum_resolve_device with a->scene->mu held.
+int accum_resolve_locked(rtx_accum* a, float* d_rgb, float* d_var, float rel_tol, hipStream_t st, uint64_t* noisy) {
+    if (noisy) HIP_TRY(hipMemsetAsync(a->noisy.ptr, 0, sizeof(unsigned long long), st));
+    const rtxd::ResolveArgs ra{a->s(), a->q(), d_rgb, d_var, noisy ? a->noisy.as<unsigned long long>() : nullptr,
+                               a->region.width, a->rows, a->tile_w_log2, a->n, rel_tol};
+    HIP_TRY(rtxd::launch_resolve(ra, st));
+    if (noisy) {
+        unsigned long long h = 0;
+        HIP_TRY(hipMemcpyAsync(&h, a->noisy.ptr, sizeof(h), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        *noisy = h;
+    }
+    return RTX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rtx_accum_create(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const rtx_region* region, rtx_accum** out) {
+    g_last_error.clear();
+    if (!s || !out) return fail(RTX_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = check_camera(cam)) return rc;
+    if (int rc = check_region(cam, region)) return rc;
+    int cur = 0;
+    HIP_TRY(hipGetDevice(&cur));
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceCopy* c = nullptr;
+    if (int rc = ensure_device(s, cur, &c)) return rc;
+    rtx_accum* a = new (std::nothrow) rtx_accum();
+    if (!a) return fail(RTX_ERR_OOM, "host memory for an accumulator");
+    a->scene = s;
+    a->device = cur;
+    a->cam = *cam;
+    a->seed = seed;
+    a->region = *region;
+    a->rows = region_rows(region);
+    a->tile_w_log2 = make_params(s, c, layout_slot(s, cam), cam, seed, region, nullptr).tile_w_log2;
+    a->slots = (uint64_t)rtxd::tiles_x_of(region->width, a->tile_w_log2) * rtxd::tiles_y_of(a->rows, a->tile_w_log2) * 64;
+    hipError_t e = a->sums.reserve(std::max<size_t>(2 * accum_bytes(a), sizeof(float)));
+    if (e == hipSuccess) e = hipMemset(a->sums.ptr, 0, a->sums.bytes);
+    if (e == hipSuccess) e = a->noisy.reserve(sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        a->sums.release();
+        delete a;
+        return fail(e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP, "the accumulator's buffers: %s", hipGetErrorString(e));
+    }
+    *out = a;
+    return RTX_OK;
+}
+
+int rtx_accum_add(rtx_accum* a, uint32_t count, void* hip_stream, uint32_t flags, rtx_stats* stats) {
+    g_last_error.clear();
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    if (count == 0) return fail(RTX_ERR_INVALID_ARG, "a pass of 0 samples");
+    if (a->n + count < a->n) return fail(RTX_ERR_INVALID_ARG, "%u + %u samples exceed 2^32 - 1", a->n, count);
+    if (int rc = accum_device(a)) return rc;
+    rtx_scene* s = a->scene;
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceCopy* c = nullptr;
+    if (int rc = ensure_device(s, a->device, &c)) return rc;
+    const rtxd::SampleRange pass{a->n, count, a->s(), a->q()};
+    uint32_t chunks = 0;
+    bool tiered = false;
+    if (int rc = enqueue_on(s, c, &a->cam, a->seed, &a->region, nullptr, (hipStream_t)hip_stream, flags, stats != nullptr,
+                            &chunks, &tiered, &pass, a->slots))
+        return rc;
+    a->n += count;
+    if (!stats) return RTX_OK;
+    const int rc = collect_on(c, (flags & RTX_FLAG_COUNTERS) != 0, (uint64_t)a->rows * a->region.width * count, chunks, stats);
+    stats->walk_layout = walk_layout(s, &a->cam, tiered);
+    return rc;
+}
+
+uint32_t rtx_accum_samples(const rtx_accum* a) { return a ? a->n : 0u; }
+
+int rtx_accum_resolve_device(rtx_accum* a, float* d_rgb, float* d_var, float rel_tol, void* hip_stream, uint64_t* noisy) {
+    g_last_error.clear();
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    if (!d_rgb && (uint64_t)a->rows * a->region.width) return fail(RTX_ERR_INVALID_ARG, "NULL output");
+    if (a->n == 0) return fail(RTX_ERR_INVALID_ARG, "nothing accumulated yet");
+    if (int rc = accum_device(a)) return rc;
+    std::lock_guard<std::mutex> lk(a->scene->mu);
+    return accum_resolve_locked(a, d_rgb, d_var, rel_tol, (hipStream_t)hip_stream, noisy);
+}
+
+int rtx_accum_resolve(rtx_accum* a, float* out_rgb, float* out_var, float rel_tol, uint64_t* noisy) {
+    g_last_error.clear();
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    const size_t bytes = (size_t)a->rows * a->region.width * 3 * sizeof(float);
+    if (!out_rgb && !noisy) return fail(RTX_ERR_INVALID_ARG, "NULL output");  // (out_rgb NULL: the count alone)
+    if (a->n == 0) return fail(RTX_ERR_INVALID_ARG, "nothing accumulated yet");
+    if (int rc = accum_device(a)) return rc;
+    std::lock_guard<std::mutex> lk(a->scene->mu);
+    std::lock_guard<std::mutex> bl(g_render_mu);  // the cached image buffers and stream
+    hipStream_t st = render_stream(a->device);
+    float* rgb = static_cast<float*>(render_buffer(a->device, -3, std::max<size_t>(1, bytes)));
+    float* var = out_var ? static_cast<float*>(render_buffer(a->device, -5, std::max<size_t>(1, bytes))) : nullptr;
+    if (!st) return fail(RTX_ERR_HIP, "stream on device %d", a->device);
+    if (!rgb || (out_var && !var)) return fail(RTX_ERR_OOM, "device buffers for a %ux%u resolve", a->region.width, a->rows);
+    // the passes may have run on any stream: every render on the device precedes the resolve (scr->last)
+    if (int rc = wait_for_renders(a->device, st)) return rc;
+    int rc = accum_resolve_locked(a, rgb, var, rel_tol, st, noisy);
+    if (rc == RTX_OK && bytes && out_rgb && copy_to_host(out_rgb, rgb, bytes, st) != hipSuccess)
+        rc = fail(RTX_ERR_HIP, "copying the resolved image to the host");
+    if (rc == RTX_OK && bytes && out_var && copy_to_host(out_var, var, bytes, st) != hipSuccess)
+        rc = fail(RTX_ERR_HIP, "copying the variance to the host");
+    (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+int rtx_accum_ppm(rtx_accum* a, char* out_text, uint64_t capacity, uint64_t* out_len) {
+    g_last_error.clear();
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    if (!out_text || !out_len) return fail(RTX_ERR_INVALID_ARG, "NULL argument");
+    if (a->n == 0) return fail(RTX_ERR_INVALID_ARG, "nothing accumulated yet");
+    if (int rc = accum_device(a)) return rc;
+    const uint32_t W = a->region.width, H = a->rows;
+    const uint64_t need = rtxd::ppm_max_bytes(W, H);
+    std::lock_guard<std::mutex> lk(a->scene->mu);
+    std::lock_guard<std::mutex> bl(g_render_mu);
+    hipStream_t st = render_stream(a->device);
+    float* rgb = static_cast<float*>(render_buffer(a->device, -3, std::max<size_t>(1, (size_t)W * H * 3 * sizeof(float))));
+    char* text = static_cast<char*>(render_buffer(a->device, -4, need));
+    if (!st) return fail(RTX_ERR_HIP, "stream on device %d", a->device);
+    if (!rgb || !text) return fail(RTX_ERR_OOM, "device buffers for a %ux%u PPM", W, H);
+    if (int rc = wait_for_renders(a->device, st)) return rc;
+    const int rc = accum_resolve_locked(a, rgb, nullptr, 0.0f, st, nullptr);
+    return ppm_to_host(rc, rgb, W, H, text, st, out_text, capacity, out_len);
+}
+
+int rtx_accum_reset(rtx_accum* a) {
+    g_last_error.clear();
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    if (int rc = accum_device(a)) return rc;
+    std::lock_guard<std::mutex> lk(a->scene->mu);
+    HIP_TRY(hipDeviceSynchronize());  // passes and resolves in flight, on any stream
+    HIP_TRY(hipMemset(a->sums.ptr, 0, a->sums.bytes));
+    a->n = 0;
+    return RTX_OK;
+}
+
+void rtx_accum_destroy(rtx_accum* a) {
+    if (!a) return;
+    {
+        DeviceGuard on(a->device);
+        if (on.error() == hipSuccess) {
+            (void)hipDeviceSynchronize();
+            a->sums.release();
+            a->noisy.release();
+        }
+    }
+    delete a;
+}
+
+}  // extern "C"

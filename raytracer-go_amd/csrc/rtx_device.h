@@ -386,7 +386,7 @@ __device__ __forceinline__ SceneRef scene_ref(const float4* base, uint32_t n_ent
 // there (randSpheres: 15.5 KB of halves + 15.6 KB of materials + one checkered texture < 32 KB),
 // else after the quad table.  (The texture record in LDS: a texture lookup used to be a chain of
 // global loads, each waiting for the wave's outstanding sample-scratch stores.)
-constexpr uint32_t LDS_B = 32768;
+// (LDS_B itself: rtx_layout.h, which the host-only units read too.)
 __host__ __device__ __forceinline__ uint32_t lds_mat_offset(uint32_t n_entries, uint32_t n_quads, uint32_t n_mats,
                                                             uint32_t n_tex) {
     const uint32_t halves = (n_entries + 1) * 16;
@@ -406,7 +406,7 @@ __device__ __forceinline__ SceneRef scene_ref_fixed(const float4* lds, uint32_t 
                     reinterpret_cast<const rtx_texture*>(lds + mo + 2 * n_mats), nullptr, nullptr, 0u, 0u};
 }
 // The LDS cache of a scene too big for the fixed layout: its first entries (the ones the walk
-// reads most, rtx_capi.hip ensure_device), 'a' halves from LDS byte 0 and 'b' halves from
+// reads most, rtx_scene.hip pack_layout), 'a' halves from LDS byte 0 and 'b' halves from
 // HOT_B (reached by the ds_read offset field, as in the fixed layout).  Up to HOT_ENTRIES_8W
 // three 8-wave workgroups share a CU; up to HOT_ENTRIES_MAX (80 KB: half of the CU's 160 KB)
 // two 12-wave ones do — 6 waves per SIMD either way.  (2560 entries against 2048)
@@ -426,14 +426,27 @@ __host__ __device__ __forceinline__ uint32_t lds_hot_bytes(uint32_t n_hot) { ret
 __host__ __device__ __forceinline__ uint32_t scene_float4s(uint32_t n_entries, uint32_t n_quads) {
     return 2 * (n_entries + 1) + 4 * n_quads;
 }
-// Device material recoding (rtx_capi.hip ensure_device): a Lambertian / DiffuseLight
+// Device material recoding (rtx_render.hip upload_copy): a Lambertian / DiffuseLight
 // whose texture is a SolidColor holds the colour in `albedo` and this texture index.
 constexpr uint32_t RTX_DEV_TEX_INLINE = 0xFFFFFFFFu;
 
 // ---------------------------------------------------------------------------------
 // Kernel parameters
 // ---------------------------------------------------------------------------------
-constexpr uint32_t COUNTER_SLOTS = 26;  // device stats slots (rtx_capi.hip collect_on)
+// Device stats slots (u64 each; rtx_render.hip collect_on reads them into rtx_stats).  Three hold a 32-bit word in
+// their low half that the kernels claim from: the unit-queue head, the defer count and the redo count.
+enum CounterSlot : uint32_t {
+    CNT_SAMPLES = 0, CNT_SEGMENTS, CNT_NODE_VISITS, CNT_PRIM_TESTS, CNT_HITS, CNT_TEXEL_FETCHES, CNT_RNG_DRAWS,
+    CNT_UNIT_HEAD,  // u32 word: Params::tile_counter
+    CNT_WAVE_ITERS, CNT_LANE_STEPS, CNT_SHADE_PHASES, CNT_SHADE_LANES, CNT_TRAV_CYCLES, CNT_SHADE_CYCLES,
+    CNT_IDLE_LANES, CNT_CACHE_HITS, CNT_PARKED_LANES, CNT_DEFERRED_LANES,
+    CNT_SHADE_SPLIT,  // 4 slots: rtx_stats::shade_split_cycles
+    CNT_DEFER_COUNT = CNT_SHADE_SPLIT + 4,  // u32 word: Params::defer_count
+    CNT_DEFERRED_PATHS, CNT_REDO_CHUNKS,
+    CNT_REDO_COUNT,  // u32 word: Params::redo_count
+    COUNTER_SLOTS
+};
+static_assert(CNT_UNIT_HEAD == 7 && CNT_DEFER_COUNT == 22 && COUNTER_SLOTS == 26, "the slots' order is rtx_stats'");
 
 struct Params {
     const float4* entries;   // n_entries + 1 'a' halves, as many 'b', 4 * n_quads (SceneRef)
@@ -528,7 +541,7 @@ __host__ __device__ __forceinline__ bool pool_fits(const Params& p) {
     return p.cam_pool && (size_t)pool_f4_offset(p) * 16 + RTX_POOL_WAVES * POOL_BYTES_PER_WAVE <= 80u * 1024u;
 }
 
-// The words of Params::error_flag, the device's sticky error word (rtx_capi.hip KernErr): counters
+// The words of Params::error_flag, the device's sticky error word (rtx_resources.hip KernErr): counters
 // the kernel only adds to and no render zeroes, so a failed render stays visible behind any renders enqueued after
 // it, until collect_on or rtx_device_check reads them (and turns a change into RTX_ERR_HIP).
 constexpr uint32_t KERR_WATCHDOG = 0u;      // waves that outlived RTX_WATCHDOG_S
@@ -1538,7 +1551,7 @@ __device__ __forceinline__ uint32_t trav_step_batched(Trav& t, const Ray& r, con
 // increase along a walk (a scene in the LDS copy stores its primitives first), but every step
 // moves a lane to a later entry of the threaded pre-order (a node's next is its first child, its
 // escape the entry after its subtree; a primitive's next the entry after it), the upload emits
-// that order from an acyclic tree (check_acyclic, rtx_capi.hip), and the sentinel ends it: every
+// that order from an acyclic tree (check_acyclic, rtx_scene.hip), and the sentinel ends it: every
 // lane reaches the sentinel within n_entries steps.  The watchdog (RTX_WATCHDOG_S) is checked
 // only between phases in render_items' loop and cannot interrupt this asm loop.
 #define RTX_WALK_VOTE                                                        \
@@ -1764,7 +1777,7 @@ __device__ __forceinline__ bool shade(const Params& p, const SceneRef E, const T
         return false;
     }
     if (m.type == RTX_MAT_DIELECTRIC) {                         // materials.go:91-113
-        // 1/ior and both r0 values precomputed per material (ensure_device, rtx_capi.hip)
+        // 1/ior and both r0 values precomputed per material (upload_copy, rtx_render.hip)
         const float eta = front ? m.albedo[0] : m.ior;
         const float d = dot(scale(ud, -1.0f), n);
         const float cos_t = d < 1.0f ? d : (d != d ? d : 1.0f); // float32(math.Min(float64(d), 1))

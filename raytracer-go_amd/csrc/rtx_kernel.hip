@@ -88,21 +88,21 @@ __device__ __forceinline__ bool dbg_skip(const Params& p, uint32_t site, uint32_
 }
 
 __device__ __forceinline__ void flush_counters(const Params& p, uint64_t samples, const Counters& cnt) {
-    atomicAdd(&p.counters[0], (unsigned long long)samples);
-    atomicAdd(&p.counters[1], (unsigned long long)cnt.segments);
-    atomicAdd(&p.counters[2], (unsigned long long)cnt.node_visits);
-    atomicAdd(&p.counters[3], (unsigned long long)cnt.prim_tests);
-    atomicAdd(&p.counters[4], (unsigned long long)cnt.hits);
-    atomicAdd(&p.counters[5], (unsigned long long)cnt.texel_fetches);
-    atomicAdd(&p.counters[6], (unsigned long long)cnt.draws);
-    if (cnt.cache_hits) atomicAdd(&p.counters[15], (unsigned long long)cnt.cache_hits);
+    atomicAdd(&p.counters[CNT_SAMPLES], (unsigned long long)samples);
+    atomicAdd(&p.counters[CNT_SEGMENTS], (unsigned long long)cnt.segments);
+    atomicAdd(&p.counters[CNT_NODE_VISITS], (unsigned long long)cnt.node_visits);
+    atomicAdd(&p.counters[CNT_PRIM_TESTS], (unsigned long long)cnt.prim_tests);
+    atomicAdd(&p.counters[CNT_HITS], (unsigned long long)cnt.hits);
+    atomicAdd(&p.counters[CNT_TEXEL_FETCHES], (unsigned long long)cnt.texel_fetches);
+    atomicAdd(&p.counters[CNT_RNG_DRAWS], (unsigned long long)cnt.draws);
+    if (cnt.cache_hits) atomicAdd(&p.counters[CNT_CACHE_HITS], (unsigned long long)cnt.cache_hits);
 }
 
 __device__ __forceinline__ void flush_sched(const Params& p, uint64_t wi, uint64_t ls, uint64_t sp, uint64_t sl) {
-    atomicAdd(&p.counters[8], (unsigned long long)wi);
-    atomicAdd(&p.counters[9], (unsigned long long)ls);
-    atomicAdd(&p.counters[10], (unsigned long long)sp);
-    atomicAdd(&p.counters[11], (unsigned long long)sl);
+    atomicAdd(&p.counters[CNT_WAVE_ITERS], (unsigned long long)wi);
+    atomicAdd(&p.counters[CNT_LANE_STEPS], (unsigned long long)ls);
+    atomicAdd(&p.counters[CNT_SHADE_PHASES], (unsigned long long)sp);
+    atomicAdd(&p.counters[CNT_SHADE_LANES], (unsigned long long)sl);
 }
 
 // ------------------------------------------------------------------------------------
@@ -264,7 +264,7 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
     static_assert(!POOL || (USE_LDS && (TIER == 0 || TIER == 1)), "the camera-ray pool: LDS scenes, near pass or one walk");
     if constexpr (TIER == 3) {
         if (__builtin_amdgcn_readfirstlane(*(volatile uint32_t*)p.redo_count) == 0u) return;
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&p.counters[24], 1ull);  // chunks with a redo
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&p.counters[CNT_REDO_CHUNKS], 1ull);  // chunks with a redo
     }
     // walk steps between two wave votes (A/B with primitive batching: 4 +0.7 %, 8 +0.8 %, 12 +1.3 %)
     constexpr uint32_t WAVE_BLOCK = 64 * WAVES, STEPS = RTX_WALK_STEPS;
@@ -329,7 +329,7 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
     const uint64_t n_units = TIER == 2 ? (uint64_t)((n_rec + 63u) / 64u)
                                        : (listed ? (uint64_t)((n_ids + 63u) / 64u) : (uint64_t)n_tiles * nsub);
     if (TIER == 2 && (DRAIN || blockIdx.x == 0) && threadIdx.x == 0 && n_rec)
-        atomicAdd(&p.counters[23], (unsigned long long)n_rec);  // deferred paths, all chunks
+        atomicAdd(&p.counters[CNT_DEFERRED_PATHS], (unsigned long long)n_rec);  // deferred paths, all chunks
     const size_t tile_floats = (size_t)n_tiles * 64 * 3;  // one sample of every tile (tile-major scratch)
     const uint64_t* const redo64 = reinterpret_cast<const uint64_t*>(p.redo_bits);  // redo pass: 64 slots a word
 
@@ -710,18 +710,18 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
         flush_counters(p, items_done, cnt);
         if (lane == 0) {
             flush_sched(p, wave_iters, lane_steps / STEPS, shade_phases, shade_lanes);
-            atomicAdd(&p.counters[14], (unsigned long long)idle_lanes);
-            atomicAdd(&p.counters[16], (unsigned long long)(parked / STEPS));
-            atomicAdd(&p.counters[17], (unsigned long long)(deferred / STEPS));
+            atomicAdd(&p.counters[CNT_IDLE_LANES], (unsigned long long)idle_lanes);
+            atomicAdd(&p.counters[CNT_PARKED_LANES], (unsigned long long)(parked / STEPS));
+            atomicAdd(&p.counters[CNT_DEFERRED_LANES], (unsigned long long)(deferred / STEPS));
         }
     }
     if (TIME && lane == 0) {
-        atomicAdd(&p.counters[12], (unsigned long long)trav_cycles);
+        atomicAdd(&p.counters[CNT_TRAV_CYCLES], (unsigned long long)trav_cycles);
         for (int q = 0; q < 4; ++q) {
             shade_cycles += split[q];
-            atomicAdd(&p.counters[18 + q], (unsigned long long)split[q]);
+            atomicAdd(&p.counters[CNT_SHADE_SPLIT + q], (unsigned long long)split[q]);
         }
-        atomicAdd(&p.counters[13], (unsigned long long)shade_cycles);
+        atomicAdd(&p.counters[CNT_SHADE_CYCLES], (unsigned long long)shade_cycles);
     }
 }
 

@@ -28,14 +28,14 @@
 // radius*radius is the float32 product hittables.go:100 computes, precomputed.
 // On the device the halves live in two arrays (all a, then all b: rtxd::SceneRef), so
 // a wave's gathers spread over every LDS bank group, and the integer words are recoded
-// so that a step needs no index arithmetic (rtx_capi.hip, ensure_device):
+// so that a step needs no index arithmetic (rtx_scene.hip, pack_layout):
 //   positions are byte offsets, 16 * index (rtxd::Trav::i);
 //   node:   a.w = escape position, b.w = next position  (b.w >= 0 <=> node)
 //   sphere: b.z = next position, b.w = RTX_DEV_SPHERE(material) = -3 - material
 //   quad:   b.z = next position, b.w = RTX_E_QUAD
 // Since every entry names its successor, the storage order is free: it is the walk order,
 // except that a scene too big for the LDS copy stores its top levels first (v3 caches those
-// in LDS; ensure_device).  The walk order, and so every test and its result, is unchanged.
+// in LDS; pack_layout).  The walk order, and so every test and its result, is unchanged.
 // Each array ends with one extra entry, the sentinel at index n: a node with an empty
 // box whose escape and next are both its own position.  Every walk ends there and a
 // step on it changes nothing, whatever the ray (NaN included), so lanes that are not
@@ -54,3 +54,9 @@ struct rtx_entry {
     float b[4];
 };
 static_assert(sizeof(rtx_entry) == 32, "entry is 32 B");
+
+// Bytes of each half's array in the LDS copy of a scene (rtx_device.h): a scene of n entries lives there when
+// (n + 1) * 16 <= LDS_B, and its storage order depends on that (rtx_scene.hip pack_layout).
+namespace rtxd {
+constexpr uint32_t LDS_B = 32768;
+}

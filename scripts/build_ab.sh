@@ -13,8 +13,8 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-ma
 cd raytracer-go_amd
 $HIPCC $FLAGS -Xclang -target-feature -Xclang -packed-fp32-ops -c csrc/rtx_kernel.hip -o ../$B/rtx_kernel.o 2>&1 |
     grep -v "packed-fp32-ops' is not a recognized feature" || true
-for f in rtx_capi rtx_ppm rtx_bvh rtx_topology rtx_collapse; do
-    $HIPCC $FLAGS -c csrc/$f.hip -o ../$B/$f.o &
+for f in $(ls csrc/*.hip | grep -v /rtx_kernel.hip); do  # every other unit
+    $HIPCC $FLAGS -c $f -o ../$B/$(basename $f .hip).o &
 done
 wait
 $HIPCC $FLAGS -shared -o ../abl/librtx_$NAME.so ../$B/*.o -Wl,-rpath,/opt/rocm/lib

@@ -10,6 +10,7 @@ HIPFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast
 /opt/rocm/bin/hipcc $HIPFLAGS "$@" -Xclang -target-feature -Xclang -packed-fp32-ops -c raytracer-go_amd/csrc/rtx_kernel.hip \
     -o abl/build_$NAME/rtx_kernel.o 2>&1 | { grep -v "packed-fp32-ops' is not a recognized feature" || true; }
 B=raytracer-go_amd/build
-/opt/rocm/bin/hipcc $HIPFLAGS -shared -o abl/librtx_$NAME.so abl/build_$NAME/rtx_kernel.o $B/rtx_capi.o $B/rtx_ppm.o \
-    $B/rtx_bvh.o $B/rtx_topology.o $B/rtx_collapse.o -Wl,-rpath,/opt/rocm/lib
+# every object of the in-tree library but its megakernel (and the claim-guard test library's)
+/opt/rocm/bin/hipcc $HIPFLAGS -shared -o abl/librtx_$NAME.so abl/build_$NAME/rtx_kernel.o \
+    $(ls $B/*.o | grep -v '/rtx_kernel') -Wl,-rpath,/opt/rocm/lib
 echo "abl/librtx_$NAME.so"

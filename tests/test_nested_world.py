@@ -1,7 +1,7 @@
 """A World nested inside the tree (ABI 5 list refs): a World handed to NewBVH as a child
 (hittables.go:39-76, bvh.go:142-185).  (*World).Hit scans its items in Add order with a
 running closest bound (hittables.go:55-72); on the device the items' entries simply follow
-one another in the threaded walk (rtx_capi.hip emit).
+one another in the threaded walk (rtx_scene.hip emit).
 
 CPU: the flattener's list refs, the C-ABI's checks on them, and two equivalences the
 reference's semantics imply, checked on the oracle: a list of one item renders exactly as
