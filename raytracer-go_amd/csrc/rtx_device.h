@@ -326,8 +326,9 @@ __device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c
     return U4{c0, c1, c2, c3};
 }
 __device__ __forceinline__ float unit_f32(uint32_t w) { return (float)(w >> 8) * 0x1.0p-24f; }
-// RandF32N(-1, 1), math.go:30-32: -1 + u * (1 - (-1)).
-__device__ __forceinline__ float signed_unit(uint32_t w) { return -1.0f + unit_f32(w) * 2.0f; }
+// RandF32N(-1, 1), math.go:30-32: -1 + u * (1 - (-1)).  u * 2 is exact (u = n * 2^-24, n < 2^24), so the two
+// multiplies are one by 2^-23: the same bits, one VALU fewer per word.
+__device__ __forceinline__ float signed_unit(uint32_t w) { return -1.0f + (float)(w >> 8) * 0x1.0p-23f; }
 
 struct PathRng {
     uint32_t k0, k1, pixel, sample;
@@ -356,6 +357,10 @@ struct Scatter {
 
 __device__ __forceinline__ uint32_t lane_pull(uint32_t src_lane, uint32_t v) {
     return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src_lane * 4u), (int)v);
+}
+// The number of set bits of a wave mask below the calling lane (v_mbcnt_lo + v_mbcnt_hi).
+__device__ __forceinline__ uint32_t rank_below(uint64_t m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
 // The scene's entries (rtx_layout.h) as two arrays of half-entries: a[i] and b[i].  An
@@ -679,28 +684,44 @@ __device__ __forceinline__ uint32_t hit_material(const SceneRef E, uint32_t hit)
     return RTX_DEV_SPHERE_MATERIAL(__float_as_int(b.w));
 }
 
-// One round of a wave-cooperative rejection loop (coop_scatter, coop_disk): the np lanes still rejecting (`pend`)
-// get K = 64 / np consecutive lanes each.  Lane i evaluates attempt base + k of lane `owner` when `slot`; an owner
-// (`mine`, the below-th pending lane) then finds its K results at bits below * K .. of the round's ballot.
+// One round of a wave-cooperative rejection loop (coop_scatter, coop_disk): the np lanes still rejecting (`pend`,
+// the ballot of the caller's `mine`) get K = 64 / np consecutive lanes each.  Lane i evaluates attempt base + k of
+// lane `owner` when `slot`; an owner (`mine`, the below-th pending lane) then finds its K results at bits
+// below * K .. of the round's ballot.
+// A round's time follows the VALU instructions it issues, so what is wave-uniform stays off the
+// VALU: K and 1 / K come from a table indexed by np (two scalar loads), `mine` is the caller's own predicate
+// instead of the lane's bit of `pend`, and the rank is v_mbcnt.
 struct CoopRound {
     uint32_t K, below, k, owner;
     bool mine, slot;
 };
-__device__ __forceinline__ CoopRound coop_round(uint64_t pend, uint32_t lane, uint64_t below_mask) {
-    const uint32_t np = (uint32_t)__popcll(pend);
-    // K = 64 / np attempts per owner this round, and q = lane / K below, by float reciprocals:
-    // 64.5 / np and (lane + 0.5) / K lie at least 1/128 from the next integer, far beyond
-    // v_rcp_f32's 1-ulp error, so truncation gives the integer quotients (the compiler's
-    // integer divisions took ~25 VALU per round).
-    const uint32_t K = __builtin_amdgcn_readfirstlane((uint32_t)(64.5f * __builtin_amdgcn_rcpf((float)np)));
-    const bool mine = (pend >> lane) & 1ull;
-    const uint32_t below = (uint32_t)__popcll(pend & below_mask);
+struct CoopK {
+    uint32_t K[65];
+    float inv[65];
+};
+constexpr CoopK make_coop_k() {
+    CoopK t{};
+    for (uint32_t n = 1; n <= 64; ++n) {
+        t.K[n] = 64u / n;
+        t.inv[n] = 1.0f / (float)(64u / n);
+    }
+    return t;
+}
+__device__ __forceinline__ CoopRound coop_round(uint64_t pend, bool mine, uint32_t lane) {
+    static constexpr CoopK T = make_coop_k();
+    const uint32_t np = (uint32_t)__popcll(pend);  // 1..64: the caller's loop runs while pend != 0
+    const uint32_t K = T.K[np];
+    const uint32_t below = rank_below(pend);
     // Lane q (< np) learns the lane id of the q-th pending lane (a permutation push).
     const uint32_t dst = mine ? below : np + (lane - below);
     const uint32_t owner_of = (uint32_t)__builtin_amdgcn_ds_permute((int)(dst * 4u), (int)lane);
-    const uint32_t q = (uint32_t)(((float)lane + 0.5f) * __builtin_amdgcn_rcpf((float)K)), k = lane - q * K;
+    // q = lane / K by the float reciprocal: (lane + 0.5) / K lies at least 1/128 from the next integer, far beyond
+    // the rounding of 1 / K and of the product, so truncation gives the integer quotient (the compiler's integer
+    // division took ~25 VALU per round)
+    const uint32_t q = (uint32_t)(((float)lane + 0.5f) * T.inv[np]), k = lane - q * K;
     const bool slot = q < np;
-    const uint32_t owner = lane_pull(slot ? q : 0u, owner_of);
+    // (a lane that is no slot pulls too, from lane q <= 63: what it evaluates is masked out of the round's ballot)
+    const uint32_t owner = lane_pull(q, owner_of);
     return CoopRound{K, below, k, owner, mine, slot};
 }
 // The owner's FIRST accepted attempt of the round, given the ballot `good` of the slots that accepted: attempt
@@ -726,30 +747,30 @@ __device__ __forceinline__ CoopPick coop_pick(const CoopRound& r, uint64_t good,
 // lanes), the n lanes still rejecting get 64/n consecutive lanes each, which evaluate
 // attempts base .. base+64/n-1 of that owner in one round; the owner takes the first
 // accepted one.  Same attempt, same bits, about 3 Philox rounds per phase.
-// b0 = block (e, 0) of a lane with hit >= 0, drawn by the caller.
 template <bool QUADS>
 __device__ __forceinline__ Scatter coop_scatter(const Params& p, const SceneRef E, const PathRng& rng,
-                                                uint32_t e, int32_t hit, const U4 b0) {
+                                                uint32_t e, int32_t hit) {
     Scatter out{v3(0.0f, 0.0f, 0.0f), 0u, 0u};
-    bool need = false;
     float x = 0.0f, y = 0.0f, z = 0.0f;
     uint32_t ty = 0xFFFFFFFFu;  // (no hit: no material)
     if (hit >= 0) {
         const uint32_t mi = hit_material<QUADS>(E, (uint32_t)hit);
         ty = E.m[mi].type;
+        const U4 b0 = rng.block(e, 0u);
         out.u0 = b0.x;
         x = signed_unit(b0.x);
         y = signed_unit(b0.y);
         z = signed_unit(b0.z);
     }
     static_assert(RTX_MAT_LAMBERTIAN == 0 && RTX_MAT_METAL == 1, "need: one unsigned compare");
-    need = ty < 2u;  // Lambertian or Metal (a single compare: its ballot needs no lane-mask materialisation)
+    const bool need = ty < 2u;  // Lambertian or Metal (a single compare: its ballot needs no lane-mask materialisation)
     uint32_t att = 0;
-    uint64_t pend = ballot(need) & ~ballot(x * x + y * y + z * z < 1.0f);  // lensq(v) < 1
+    const bool ok0 = x * x + y * y + z * z < 1.0f;  // lensq(v) < 1
+    bool pending = need && !ok0;
+    uint64_t pend = ballot(need) & ~ballot(ok0);  // = ballot(pending)
     const uint32_t lane = __lane_id();
-    const uint64_t below_mask = (1ull << lane) - 1ull;
     for (uint32_t base = 1; pend != 0;) {
-        const CoopRound cr = coop_round(pend, lane, below_mask);
+        const CoopRound cr = coop_round(pend, pending, lane);
         const uint32_t opix = lane_pull(cr.owner, rng.pixel), osmp = lane_pull(cr.owner, rng.sample);
         const uint32_t oe = lane_pull(cr.owner, e);
         const U4 b = philox4x32_10(opix, osmp, oe, base + cr.k, rng.k0, rng.k1);
@@ -765,7 +786,8 @@ __device__ __forceinline__ Scatter coop_scatter(const Params& p, const SceneRef 
             z = fz;
             att = base + pk.kk;
         }
-        pend &= ~ballot(pk.found);  // (ballot(mine) is pend)
+        pending = pending && !pk.found;
+        pend &= ~ballot(pk.found);
         base += cr.K;
     }
     if (need) {
@@ -786,9 +808,8 @@ __device__ __forceinline__ Scatter coop_scatter(const Params& p, const SceneRef 
 __device__ __forceinline__ void coop_disk(const PathRng& cr, bool pending, float& x, float& y, uint32_t& att) {
     uint64_t pend = ballot(pending);
     const uint32_t lane = __lane_id();
-    const uint64_t below_mask = (1ull << lane) - 1ull;
     for (uint32_t base = 1; pend != 0;) {
-        const CoopRound rd = coop_round(pend, lane, below_mask);
+        const CoopRound rd = coop_round(pend, pending, lane);
         const uint32_t opix = lane_pull(rd.owner, cr.pixel);
         const U4 b = philox4x32_10(opix, cr.sample, 0u, base + rd.k, cr.k0, cr.k1);
         const float bx = signed_unit(b.x), by = signed_unit(b.y);
@@ -801,6 +822,7 @@ __device__ __forceinline__ void coop_disk(const PathRng& cr, bool pending, float
             y = fy;
             att = base + pk.kk;
         }
+        pending = pending && !pk.found;
         pend &= ~ballot(pk.found);
         base += rd.K;
     }

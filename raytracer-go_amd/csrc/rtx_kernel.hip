@@ -501,11 +501,8 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
             defer(bad);
         }
         Scatter sc{v3(0.0f, 0.0f, 0.0f), 0u, 0u};
-        if (!mini) {  // (a miss phase draws nothing)
-            U4 b0{0u, 0u, 0u, 0u};
-            if (mode == M_SHADE && t.hit >= 0) b0 = rng.block(seg + 1, 0u);
-            sc = coop_scatter<QUADS>(p, E, rng, seg + 1, mode == M_SHADE ? t.hit : -1, b0);
-        }
+        // (a miss phase draws nothing)
+        if (!mini) sc = coop_scatter<QUADS>(p, E, rng, seg + 1, mode == M_SHADE ? t.hit : -1);
         if (TIME) split_clk(split[0], clk);
         if (mode == M_SHADE) {
             V3 color;
