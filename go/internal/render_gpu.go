@@ -538,6 +538,133 @@ func HitBatch(world Hittable, rays []Ray, rayT []Interval) ([]HitInfo, []bool, e
 	return infos, oks, nil
 }
 
+// PathKey names the Philox blocks of one path event (rtx_path_key, rtx.h "path building blocks"): the global
+// pixel index, the sample, and the event (0 = GetRay, s + 1 = the scatter after segment s).  Draws is what
+// RayBatch reports: the rand.Float32() calls GetRay made.
+type PathKey struct {
+	Pixel, Sample, Event, Draws uint32
+}
+
+// Bounce is Material.Emit and Material.Scatter of one hit (rtx_bounce): Ray is ScatterInfo's ray, to be hit
+// with GetColor's Interval{0.001, +Inf}; Draws counts the rand.Float32() calls Scatter made.
+type Bounce struct {
+	Scattered, Emits     bool
+	Attenuation, Emitted Vec3
+	Ray                  Ray
+	Draws                uint32
+}
+
+// alignedBytes is a byte slice with room to start on a 16-B boundary, which rtx_trace, rtx_camera_rays and
+// rtx_shade want of every table and a Go slice of a 4-B aligned struct does not promise.  The caller pins
+// &buf[0] for the call (the bytes hold no Go pointers).
+func alignedBytes(bytes uintptr) ([]byte, unsafe.Pointer) {
+	buf := make([]byte, bytes+16)
+	off := (16 - uintptr(unsafe.Pointer(&buf[0]))%16) % 16
+	return buf, unsafe.Pointer(&buf[off])
+}
+
+// RayBatch is GetRay (camera.go:265-299) for samples [firstSample, firstSample + count) of every pixel on the
+// GPU (rtx_camera_rays): ray (k - firstSample) * W * H + y * W + x is the ray of pixel (x, y) and sample k under
+// the RNG contract's seed, and keys[i] is the key of its first scatter (Event 1).  Every ray is to be hit with
+// Interval{0.001, +Inf}.
+func (c *Camera) RayBatch(seed uint64, firstSample, count uint32) ([]Ray, []PathKey, error) {
+	c.init()
+	cam := c.gpuCamera()
+	region := C.rtx_region{x0: 0, y0: 0, width: cam.image_width, height: cam.image_height, rank: 0, world: 1, stripe: 0}
+	n := int(count) * int(cam.image_width) * int(cam.image_height)
+	rays, keys := make([]Ray, n), make([]PathKey, n)
+	if n == 0 {
+		return rays, keys, nil
+	}
+	rayBuf, rayPtr := alignedBytes(uintptr(n) * unsafe.Sizeof(C.rtx_ray{}))
+	keyBuf, keyPtr := alignedBytes(uintptr(n) * unsafe.Sizeof(C.rtx_path_key{}))
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pin.Pin(&rayBuf[0])
+	pin.Pin(&keyBuf[0])
+	outRays, outKeys := (*C.rtx_ray)(rayPtr), (*C.rtx_path_key)(keyPtr)
+	if rc := C.rtx_camera_rays(&cam, C.uint64_t(seed), &region, C.uint32_t(firstSample), C.uint32_t(count), outRays, outKeys); rc != 0 {
+		if gpuMissing(rc) {
+			return nil, nil, errFallback
+		}
+		return nil, nil, rtxErr(rc)
+	}
+	v3 := func(a [3]C.float) Vec3 { return NewVec3(float32(a[0]), float32(a[1]), float32(a[2])) }
+	crays, ckeys := unsafe.Slice(outRays, n), unsafe.Slice(outKeys, n)
+	for i := range rays {
+		var r C.rtx_ray = crays[i]
+		var k C.rtx_path_key = ckeys[i]
+		rays[i] = Ray{origin: v3(r.origin), dir: v3(r.dir)}
+		keys[i] = PathKey{Pixel: uint32(k.pixel), Sample: uint32(k.sample), Event: uint32(k.event), Draws: uint32(k.draws)}
+	}
+	return rays, keys, nil
+}
+
+// ScatterBatch is hit.material.Emit and hit.material.Scatter (ray.go:41-42) for a batch on the GPU (rtx_shade):
+// rays[i] is the ray that was hit, hits[i] its HitInfo as HitBatch returned it (a nil material: no hit, an all-zero
+// Bounce), keys[i] the path event whose Philox blocks the scatter draws from, seed the RNG contract's seed.  The
+// world is flattened and uploaded for the call, as in HitBatch.
+func ScatterBatch(world Hittable, rays []Ray, hits []HitInfo, keys []PathKey, seed uint64) ([]Bounce, error) {
+	if len(rays) != len(hits) || len(rays) != len(keys) {
+		return nil, errors.New("rtx: ScatterBatch needs one hit and one key per ray")
+	}
+	out := make([]Bounce, len(rays))
+	if len(rays) == 0 {
+		return out, nil
+	}
+	scene, t, err := sceneTables(world, 0)
+	if errors.Is(err, errUnsupported) {
+		return nil, errFallback
+	}
+	if err != nil {
+		return nil, err
+	}
+	defer C.rtx_scene_destroy(scene)
+	n := uintptr(len(rays))
+	rayBuf, rayPtr := alignedBytes(n * unsafe.Sizeof(C.rtx_ray{}))
+	hitBuf, hitPtr := alignedBytes(n * unsafe.Sizeof(C.rtx_hit{}))
+	keyBuf, keyPtr := alignedBytes(n * unsafe.Sizeof(C.rtx_path_key{}))
+	outBuf, outPtr := alignedBytes(n * unsafe.Sizeof(C.rtx_bounce{}))
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pin.Pin(&rayBuf[0])
+	pin.Pin(&hitBuf[0])
+	pin.Pin(&keyBuf[0])
+	pin.Pin(&outBuf[0])
+	inRays, inHits, inKeys, bounces := (*C.rtx_ray)(rayPtr), (*C.rtx_hit)(hitPtr), (*C.rtx_path_key)(keyPtr), (*C.rtx_bounce)(outPtr)
+	crays, chits, ckeys := unsafe.Slice(inRays, len(rays)), unsafe.Slice(inHits, len(rays)), unsafe.Slice(inKeys, len(rays))
+	for i := range rays {
+		crays[i] = C.rtx_ray{origin: vec(rays[i].origin), tmin: 0.001, dir: vec(rays[i].dir), tmax: C.float(math.Inf(1))}
+		ckeys[i] = C.rtx_path_key{pixel: C.uint32_t(keys[i].Pixel), sample: C.uint32_t(keys[i].Sample), event: C.uint32_t(keys[i].Event)}
+		chits[i] = C.rtx_hit{t: C.float(math.Inf(1)), prim: C.RTX_HIT_NONE}
+		mi, known := t.matIdx[hits[i].material]
+		if hits[i].material == nil || !known {
+			continue
+		}
+		front := C.uint32_t(0)
+		if hits[i].frontFace {
+			front = 1
+		}
+		// (prim only says "a hit" to rtx_shade: the material index is what it reads)
+		chits[i] = C.rtx_hit{t: C.float(hits[i].t), prim: 0, material: mi, front_face: front, point: vec(hits[i].point),
+			u: C.float(hits[i].u), normal: vec(hits[i].normal), v: C.float(hits[i].v)}
+	}
+	if rc := C.rtx_shade(scene, C.uint64_t(seed), inRays, inHits, inKeys, C.uint64_t(len(rays)), bounces, 0, nil); rc != 0 {
+		if gpuMissing(rc) {
+			return nil, errFallback
+		}
+		return nil, rtxErr(rc)
+	}
+	v3 := func(a [3]C.float) Vec3 { return NewVec3(float32(a[0]), float32(a[1]), float32(a[2])) }
+	for i, rec := range unsafe.Slice(bounces, len(rays)) {
+		var b C.rtx_bounce = rec
+		out[i] = Bounce{Scattered: b.flags&C.RTX_BOUNCE_SCATTERED != 0, Emits: b.flags&C.RTX_BOUNCE_EMITS != 0,
+			Attenuation: v3(b.attenuation), Emitted: v3(b.emitted), Draws: uint32(b.rng_draws),
+			Ray: Ray{origin: v3(b.ray.origin), dir: v3(b.ray.dir)}}
+	}
+	return out, nil
+}
+
 // gpuCamera is Camera.init's derived state (camera.go:128-165) as rtx.h's kernel constants.
 func (c *Camera) gpuCamera() C.rtx_camera {
 	return C.rtx_camera{

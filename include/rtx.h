@@ -640,6 +640,100 @@ int rtx_trace_device(rtx_scene* scene, const rtx_ray* d_rays, uint64_t n, rtx_hi
 int rtx_trace(rtx_scene* scene, const rtx_ray* rays, uint64_t n, rtx_hit* hits, uint32_t flags,
               rtx_trace_stats* stats);
 
+/* ---- path building blocks (ABI 10, additive) ---------------------
+ * The other two public calls under Render, for a batch:
+ *   Camera.GetRay                                  camera.go:265-299
+ *   Material.Emit + Material.Scatter               ray.go:41-42, materials.go:23-113, 297-313
+ * with the four textures and the Philox draw order of DESIGN.md §3, computed by the same device code as a
+ * render.  GetRay -> Hit -> Scatter in a loop is Ray.GetColor (ray.go:32-54), so with rtx_trace they compose
+ * into an integrator of the caller's own.  This loop IS a render: on a scene that keeps the caller's tree
+ * (RTX_SCENE_REFERENCE_BVH) its colours equal rtx_render*'s bit for bit (float32, each operation rounded, no fused
+ * multiply-add) and its segments, hits, draws and texel fetches are the render's; on the library's own trees a
+ * trace may resolve a rare grazing hit differently from the render's walk:
+ *
+ *   rays, keys = camera_rays(region, first, count);  T = 1;  L = 0;  alive = all
+ *   repeat max_depth times:
+ *       hits = trace(rays, RTX_TRACE_UV);  b = shade(rays, hits, keys)
+ *       miss & alive:  L += T * background;  alive = false
+ *       hit  & alive:  if EMITS: L += T * emitted
+ *                      if SCATTERED: T *= attenuation;  rays = b.ray;  keys.event += 1   else alive = false
+ *   colour(pixel) = (sum of L over k, in k order) * (1 / spp)
+ *
+ * An ended path needs no compaction: its bounce ray is all zero, tmin >= tmax is a miss in rtx_trace, and a miss
+ * shades to an all-zero bounce again. */
+typedef struct rtx_path_key { /* 16 B: the Philox counter of DESIGN.md §3 without the attempt */
+    uint32_t pixel;           /* GLOBAL pixel index y * image_width + x                          */
+    uint32_t sample;          /* k                                                               */
+    uint32_t event;           /* 0 = GetRay; s + 1 = the scatter after segment s                 */
+    uint32_t draws;           /* written by rtx_camera_rays*: rand.Float32() calls GetRay made;
+                                 ignored on input                                                */
+} rtx_path_key;
+
+typedef struct rtx_bounce { /* 64 B */
+    float attenuation[3];   /* ScatterInfo.attenuation; 0 when not scattered                       */
+    uint32_t flags;         /* RTX_BOUNCE_SCATTERED | RTX_BOUNCE_EMITS                             */
+    float emitted[3];       /* material.Emit(u, v, point): the texture of a DiffuseLight, else 0   */
+    uint32_t rng_draws;     /* rand.Float32() calls Scatter made (3 per unit-sphere attempt,
+                               1 for a Dielectric that can refract)                                */
+    rtx_ray ray;            /* ScatterInfo.ray with GetColor's interval: origin = hit.point,
+                               dir, tmin = 0.001f, tmax = +inf; all zero when not scattered        */
+} rtx_bounce;
+#define RTX_BOUNCE_SCATTERED 1u
+#define RTX_BOUNCE_EMITS 2u /* the material is a DiffuseLight */
+#define RTX_SHADE_COUNTERS 1u /* counting instantiation: hits, scattered, rng_draws, texel_fetches (with stats only) */
+typedef struct rtx_shade_stats {
+    uint64_t n;             /* records                                                             */
+    uint64_t hits;          /* RTX_SHADE_COUNTERS: records with a hit                              */
+    uint64_t scattered;     /* RTX_SHADE_COUNTERS: records with RTX_BOUNCE_SCATTERED               */
+    uint64_t rng_draws;     /* RTX_SHADE_COUNTERS: the sum of rtx_bounce.rng_draws                 */
+    uint64_t texel_fetches; /* RTX_SHADE_COUNTERS: image-texture lookups, as rtx_stats'            */
+    double kernel_ms;       /* device time of the launches, HIP events on the stream               */
+} rtx_shade_stats;
+
+/* GetRay for samples k = first_sample .. first_sample + count - 1 of every pixel of the region's shard, into
+ * device memory of the CURRENT device on the given HIP stream; returns after enqueueing.  Needs no scene.  The
+ * camera and the region are validated as by rtx_render_region_device.  With rows = rtx_region_rows(region) and
+ * P = rows * region->width, ray (k - first_sample) * P + i * width + (x - x0) belongs to pixel
+ * (x, y0 + rtx_region_row(region, i)) and sample k: sample-major, so 64 consecutive rays are neighbouring pixels
+ * of one sample.  Draws (event 0): block (0, 0) gives dx, dy and the first defocus-disk pair;
+ * attempt a >= 1 of the disk uses words 0 and 1 of block (0, a).  The disk's rejection loop runs whether or not
+ * defocus_angle > 0, as in the reference, so `draws` is the reference's count.  Every ray has tmin = 0.001f and
+ * tmax = +inf (GetColor's interval, ray.go:36).  d_keys (may be NULL) receives (y * image_width + x, k, 1, draws):
+ * event 1 is the key of the first scatter.  count == 0 or an empty shard returns RTX_OK and launches nothing.
+ * first_sample + count past 2^32 - 1, a NULL cam, region or d_rays, and a pointer not aligned to 16 B return
+ * RTX_ERR_INVALID_ARG.  More rays than one launch takes are cut into several launches. */
+int rtx_camera_rays_device(const rtx_camera* cam, uint64_t seed, const rtx_region* region, uint32_t first_sample,
+                           uint32_t count, rtx_ray* d_rays, rtx_path_key* d_keys, void* hip_stream);
+/* The same into host memory, on the current device.  Blocking. */
+int rtx_camera_rays(const rtx_camera* cam, uint64_t seed, const rtx_region* region, uint32_t first_sample,
+                    uint32_t count, rtx_ray* rays, rtx_path_key* keys);
+
+/* Emit and Scatter for n records in lock step, device memory of the CURRENT device on the given HIP stream:
+ *  - d_rays[i] is the ray that was traced (Metal and Dielectric need Unit(r.dir));
+ *  - d_hits[i] is its CLOSEST hit as rtx_trace* wrote it: point, normal, front_face, material, u and v are
+ *    HitInfo's.  A scene with image textures must be traced with RTX_TRACE_UV (u and v are 0 without it).  Hits of
+ *    RTX_TRACE_ANY are not valid input: only their prim is specified;
+ *  - d_keys[i] names the Philox block: attempt a of the unit-sphere loop (vec3.go:182-190) is words 0-2 of
+ *    (pixel, sample, event, a); the Dielectric's uniform (materials.go:103) is word 0 of (pixel, sample, event, 0),
+ *    drawn only when refraction is possible;
+ *  - seed is the render's seed.
+ * d_hits[i].prim == RTX_HIT_NONE (a miss, or the all-zero bounce ray of an ended path traced again) gives an
+ * all-zero bounce, and so does a material index outside the scene's table.  A Metal that absorbs (materials.go:70)
+ * gives flags = 0, attenuation 0 and an all-zero ray; its rng_draws still counts the draws made.
+ * Input and output buffers must not overlap.  n == 0 returns RTX_OK.  A NULL scene, a NULL pointer with n > 0, a
+ * pointer not aligned to 16 B, flag bits other than RTX_SHADE_COUNTERS (all checked before any device is touched)
+ * and a current device that holds no copy of the scene return RTX_ERR_INVALID_ARG.
+ * Returns after enqueueing unless stats != NULL; then it synchronises the stream and fills stats.  A shade takes
+ * the scene's mutex like a trace, uses none of the per-device sample scratch and keeps counters and events of its
+ * own: a counting shade between two renders changes neither's stats.  n beyond what one launch indexes in 32 bits
+ * is cut into several launches. */
+int rtx_shade_device(rtx_scene* scene, uint64_t seed, const rtx_ray* d_rays, const rtx_hit* d_hits,
+                     const rtx_path_key* d_keys, uint64_t n, rtx_bounce* d_out, uint32_t flags, void* hip_stream,
+                     rtx_shade_stats* stats);
+/* The same for records in host memory, on the current device.  Blocking. */
+int rtx_shade(rtx_scene* scene, uint64_t seed, const rtx_ray* rays, const rtx_hit* hits, const rtx_path_key* keys,
+              uint64_t n, rtx_bounce* out, uint32_t flags, rtx_shade_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

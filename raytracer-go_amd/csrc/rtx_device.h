@@ -676,6 +676,18 @@ __device__ __forceinline__ V3 texture_value(const Params& p, const SceneRef E, u
     return v3((float)(px.x & 0xFFFFu) * cs, (float)(px.x >> 16) * cs, (float)(px.y & 0xFFFFu) * cs);
 }
 
+// The same from the tables alone, for a kernel without a render's Params (rtx_shade.hip): the lookup reads
+// Params::texels and SceneRef::tx and nothing else of either.
+template <bool COUNT, bool NOISE = false>
+__device__ __forceinline__ V3 texture_value(const rtx_texture* textures, const uint32_t* texels, uint32_t ti, float u,
+                                            float v, V3 pt, Counters& cnt) {
+    Params p;
+    p.texels = texels;
+    SceneRef E{};
+    E.tx = textures;
+    return texture_value<COUNT, NOISE>(p, E, ti, u, v, pt, cnt);
+}
+
 // Material index of the primitive at entry `hit`.
 template <bool QUADS>
 __device__ __forceinline__ uint32_t hit_material(const SceneRef E, uint32_t hit) {

@@ -6,7 +6,8 @@
 //                      word, render buffers / streams / events, RCCL; rtx_release_device_memory, rtx_device_check
 //   rtx_render.hip     the scene's device copy and layouts, enqueue_on / collect_on, the region render, PPM
 //   rtx_bands.hip      rtx_render(_ex): the bands and their assembly
-//   rtx_accum.hip      progressive passes; rtx_trace_capi.hip: ray queries; rtx_capi.hip: scene create / destroy
+//   rtx_accum.hip      progressive passes; rtx_trace_capi.hip: ray queries; rtx_shade_capi.hip: camera rays and
+//                      material scatter for a batch; rtx_capi.hip: scene create / destroy
 //
 // A unit that defines RTX_HOST_ONLY before including this header sees the first half only, which names no HIP type:
 // it compiles with the plain host compiler and links without the runtime (tests/test_pack_layout.py).
@@ -137,6 +138,9 @@ struct DeviceCopy {
     DeviceBuffer rank_sphere;  // rank word of a sphere entry -> the caller's sphere index (first trace)
     DeviceBuffer trace_counters;
     hipEvent_t tev0 = nullptr, tev1 = nullptr;
+    // Path building blocks (rtx_shade_device): counters and events of their own (first shade).
+    DeviceBuffer shade_counters;
+    hipEvent_t sev0 = nullptr, sev1 = nullptr;
 
     unsigned long long* slot(uint32_t k) const { return counters.as<unsigned long long>() + k; }
     // a counter slot's low word, for the three the kernels claim from

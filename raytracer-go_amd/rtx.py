@@ -43,6 +43,10 @@ RTX_HIT_NONE = 0xFFFFFFFF  # Hit.prim of a miss
 RTX_TRACE_ANY = 1  # stop at the first accepted primitive: only prim != RTX_HIT_NONE is specified
 RTX_TRACE_UV = 2  # fill u, v
 RTX_TRACE_COUNTERS = 4  # the counting instantiation (with stats)
+# path building blocks (rtx_camera_rays*, rtx_shade*, ABI 10 additive)
+RTX_BOUNCE_SCATTERED = 1  # Bounce.flags: Scatter returned true; attenuation and ray are ScatterInfo's
+RTX_BOUNCE_EMITS = 2  # Bounce.flags: the material is a DiffuseLight; emitted is its texture
+RTX_SHADE_COUNTERS = 1  # the counting instantiation (with stats)
 
 
 def RTX_TRACE_OCTANT(o: int) -> int:
@@ -146,15 +150,35 @@ class TraceStats(ctypes.Structure):  # rtx_trace_stats
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PathKey(ctypes.Structure):  # rtx_path_key, 16 B
+    _fields_ = [("pixel", c_uint32), ("sample", c_uint32), ("event", c_uint32), ("draws", c_uint32)]
+
+
+class Bounce(ctypes.Structure):  # rtx_bounce, 64 B
+    _fields_ = [("attenuation", c_float * 3), ("flags", c_uint32), ("emitted", c_float * 3), ("rng_draws", c_uint32),
+                ("ray", TraceRay)]
+
+
+class ShadeStats(ctypes.Structure):  # rtx_shade_stats
+    _fields_ = [("n", c_uint64), ("hits", c_uint64), ("scattered", c_uint64), ("rng_draws", c_uint64),
+                ("texel_fetches", c_uint64), ("kernel_ms", c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 def __getattr__(name: str):
-    """RAY_DTYPE / HIT_DTYPE: the numpy structured dtypes of rtx_ray and rtx_hit (numpy is imported on first use,
-    as everywhere in this module)."""
-    if name in ("RAY_DTYPE", "HIT_DTYPE"):
+    """RAY_DTYPE / HIT_DTYPE / KEY_DTYPE / BOUNCE_DTYPE: the numpy structured dtypes of rtx_ray, rtx_hit, rtx_path_key
+    and rtx_bounce (numpy is imported on first use, as everywhere in this module)."""
+    if name in ("RAY_DTYPE", "HIT_DTYPE", "KEY_DTYPE", "BOUNCE_DTYPE"):
         import numpy as np
         ray = np.dtype([("origin", "<f4", (3,)), ("tmin", "<f4"), ("dir", "<f4", (3,)), ("tmax", "<f4")])
         hit = np.dtype([("t", "<f4"), ("prim", "<u4"), ("material", "<u4"), ("front_face", "<u4"),
                         ("point", "<f4", (3,)), ("u", "<f4"), ("normal", "<f4", (3,)), ("v", "<f4")])
-        globals().update(RAY_DTYPE=ray, HIT_DTYPE=hit)
+        key = np.dtype([("pixel", "<u4"), ("sample", "<u4"), ("event", "<u4"), ("draws", "<u4")])
+        bounce = np.dtype([("attenuation", "<f4", (3,)), ("flags", "<u4"), ("emitted", "<f4", (3,)),
+                           ("rng_draws", "<u4"), ("ray", ray)])
+        globals().update(RAY_DTYPE=ray, HIT_DTYPE=hit, KEY_DTYPE=key, BOUNCE_DTYPE=bounce)
         return globals()[name]
     raise AttributeError(f"module 'rtx' has no attribute {name!r}")
 
@@ -172,6 +196,8 @@ RTX_SYMBOLS = [
     "rtx_accum_ppm", "rtx_accum_reset", "rtx_accum_destroy",
     # ray queries (ABI 10, additive)
     "rtx_trace_device", "rtx_trace",
+    # path building blocks (ABI 10, additive)
+    "rtx_camera_rays_device", "rtx_camera_rays", "rtx_shade_device", "rtx_shade",
 ]
 RTXHOST_SYMBOLS = [
     "rtxhost_build_scene", "rtxhost_scene_free", "rtxhost_scene_desc", "rtxhost_scene_camera",
@@ -289,6 +315,18 @@ def load() -> ctypes.CDLL:
         L.rtx_trace_device.restype = c_int
         L.rtx_trace.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(TraceStats)]
         L.rtx_trace.restype = c_int
+    if hasattr(L, "rtx_shade_device"):  # ABI 10, additive (RTX_LIB may name an older build for A/B)
+        L.rtx_camera_rays_device.argtypes = [POINTER(Camera), c_uint64, POINTER(Region), c_uint32, c_uint32, c_void_p,
+                                             c_void_p, c_void_p]
+        L.rtx_camera_rays_device.restype = c_int
+        L.rtx_camera_rays.argtypes = [POINTER(Camera), c_uint64, POINTER(Region), c_uint32, c_uint32, c_void_p, c_void_p]
+        L.rtx_camera_rays.restype = c_int
+        L.rtx_shade_device.argtypes = [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32,
+                                       c_void_p, POINTER(ShadeStats)]
+        L.rtx_shade_device.restype = c_int
+        L.rtx_shade.argtypes = [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32,
+                                POINTER(ShadeStats)]
+        L.rtx_shade.restype = c_int
     _lib = L
     return L
 
@@ -564,6 +602,43 @@ class DeviceScene:
         out = out.reshape(rays.shape)
         return (out, st) if stats else out
 
+    def shade_device(self, seed: int, rays_ptr: int, hits_ptr: int, keys_ptr: int, n: int, out_ptr: int, flags: int = 0,
+                     stream: int = 0, stats: bool = False):
+        """rtx_shade_device: n records of rtx_ray / rtx_hit / rtx_path_key in lock step -> n rtx_bounce at out_ptr,
+        device memory of the current device (16-B aligned).  Enqueues and returns None, or with stats=True waits and
+        returns the ShadeStats (flags | RTX_SHADE_COUNTERS fills its work counters)."""
+        st = ShadeStats() if stats else None
+        check(load().rtx_shade_device(self._h, seed, c_void_p(rays_ptr), c_void_p(hits_ptr), c_void_p(keys_ptr), n,
+                                      c_void_p(out_ptr), flags, c_void_p(stream),
+                                      ctypes.byref(st) if st is not None else None), "rtx_shade_device")
+        return st
+
+    def shade(self, rays, hits, keys, seed: int, stats: bool = False, flags: int = 0):
+        """rtx_shade: numpy arrays of RAY_DTYPE, HIT_DTYPE and KEY_DTYPE of one shape in, an array of BOUNCE_DTYPE of
+        that shape out (and the ShadeStats with stats=True, counters filled with flags=RTX_SHADE_COUNTERS).
+        Blocking."""
+        import numpy as np
+        types = [__getattr__(t) for t in ("RAY_DTYPE", "HIT_DTYPE", "KEY_DTYPE")]
+        arrs = [np.asarray(a) for a in (rays, hits, keys)]
+        for a, t, what in zip(arrs, types, ("rays", "hits", "keys")):
+            if a.dtype != t:
+                raise TypeError(f"{what} must have dtype {t}, not {a.dtype}")
+            if a.shape != arrs[0].shape:
+                raise ValueError("rays, hits and keys must have one shape")
+        n = arrs[0].size
+        src = []
+        for a, t in zip(arrs, types):  # 16-B aligned copies
+            b = _aligned_empty(n, t)
+            b[...] = a.reshape(-1)
+            src.append(b)
+        out = _aligned_empty(n, __getattr__("BOUNCE_DTYPE"))
+        st = ShadeStats() if stats else None
+        check(load().rtx_shade(self._h, seed, *[b.ctypes.data_as(c_void_p) for b in src], n,
+                               out.ctypes.data_as(c_void_p), flags, ctypes.byref(st) if st is not None else None),
+              "rtx_shade")
+        out = out.reshape(arrs[0].shape)
+        return (out, st) if stats else out
+
     def accumulator(self, cam: Camera, seed: int, region: Region) -> "Accumulator":
         """rtx_accum_create on the current device: progressive passes over `region` (close it before the scene)."""
         return Accumulator(self, cam, seed, region)
@@ -656,6 +731,30 @@ def _aligned_empty(n: int, dtype):
     raw = np.empty(n * dtype.itemsize + 16, np.uint8)
     off = (-raw.ctypes.data) % 16
     return raw[off: off + n * dtype.itemsize].view(dtype)
+
+
+def camera_rays_device(cam: Camera, seed: int, region: Region, first: int, count: int, rays_ptr: int, keys_ptr: int = 0,
+                       stream: int = 0) -> None:
+    """rtx_camera_rays_device: GetRay of samples [first, first + count) of the region's shard into device memory of
+    the current device, sample-major (record (k - first) * P + i * width + x - x0); keys_ptr may be 0.  Enqueues."""
+    check(load().rtx_camera_rays_device(ctypes.byref(cam), seed, ctypes.byref(region), first, count, c_void_p(rays_ptr),
+                                        c_void_p(keys_ptr) if keys_ptr else None, c_void_p(stream)),
+          "rtx_camera_rays_device")
+
+
+def camera_rays(cam: Camera, seed: int, region: Region, first: int = 0, count=None):
+    """rtx_camera_rays: (rays, keys), arrays of RAY_DTYPE and KEY_DTYPE of shape (count, rows, width); count defaults
+    to the camera's samples_per_pixel.  Blocking."""
+    if count is None:
+        count = cam.samples_per_pixel
+    rows = region_rows(region)
+    n = count * rows * region.width
+    rays = _aligned_empty(n, __getattr__("RAY_DTYPE"))
+    keys = _aligned_empty(n, __getattr__("KEY_DTYPE"))
+    check(load().rtx_camera_rays(ctypes.byref(cam), seed, ctypes.byref(region), first, count,
+                                 rays.ctypes.data_as(c_void_p), keys.ctypes.data_as(c_void_p)), "rtx_camera_rays")
+    shape = (count, rows, region.width)
+    return rays.reshape(shape), keys.reshape(shape)
 
 
 def release_device_memory(device: int = -1) -> None:

@@ -1,0 +1,86 @@
+"""A wavefront path tracer in thirty lines of torch over the library's path building blocks (include/rtx.h, "path
+building blocks"): rtx_camera_rays_device -> (rtx_trace_device -> rtx_shade_device) x max_depth.
+
+This is Ray.GetColor (ray.go:32-54) of the reference with the recursion turned into rounds over all paths at once.  It
+is the example an integrator of one's own starts from (a light tracer, an AOV pass, direct lighting with RTX_TRACE_ANY
+shadow rays, a torch-side estimator), and the loop the tests hold to the oracle: on a scene that keeps the caller's
+tree its image equals rtx_render_region_device's bit for bit on every pixel, because camera rays, hits and scatters
+are computed by the render's own device code and the colour arithmetic below is the render's: float32, one rounding
+per multiply and per add, in the same order (torch's eager `a * b` and `a + b` are separate kernels; nothing here may
+be replaced by addcmul or a compiled graph that fuses them).  On the library's own trees a trace may resolve a rare
+grazing hit differently from the render's walk: 4 pixels of a 1920x1080x8 frame.
+
+The megakernel renders the same frame many times faster (scripts/shade_rates.py measures how much): every round here
+reads and writes each path's records in HBM and launches a dozen small torch kernels."""
+from __future__ import annotations
+
+import rtx
+
+_MISS = -1  # RTX_HIT_NONE seen through an int32 view
+
+
+def render(dev: "rtx.DeviceScene", cam: "rtx.Camera", seed: int, region: "rtx.Region", compact: bool = False,
+           counters: bool = False):
+    """The region's shard rendered on the current device: a float32 torch tensor [rows, width, 3] there (on the
+    caller's tree every value is the one rtx_render_region_device gives).  compact=True drops ended paths between rounds (torch indexing) instead
+    of carrying them as misses.  counters=True also returns the dict of sums {segments, hits, rng_draws,
+    texel_fetches} of the render's rtx_stats (each round then waits for its counting shade)."""
+    import torch
+
+    stream = torch.cuda.current_stream().cuda_stream
+    cuda = torch.device("cuda", torch.cuda.current_device())
+    rows, width, spp = rtx.region_rows(region), region.width, cam.samples_per_pixel
+    n = spp * rows * width
+    L = torch.zeros((n, 3), dtype=torch.float32, device=cuda)
+    work = {"segments": 0, "hits": 0, "rng_draws": 0, "texel_fetches": 0}
+    if n:
+        # records as rows of 32-bit words: ray 8, key 4, hit 12, bounce 16 (rtx.h); torch allocations are 16-B aligned
+        rays = torch.empty((n, 8), dtype=torch.float32, device=cuda)
+        keys = torch.empty((n, 4), dtype=torch.int32, device=cuda)
+        hits = torch.empty((n, 12), dtype=torch.int32, device=cuda)
+        bounce = torch.empty((n, 16), dtype=torch.float32, device=cuda)
+        rtx.camera_rays_device(cam, seed, region, 0, spp, rays.data_ptr(), keys.data_ptr(), stream)
+        if counters:
+            work["rng_draws"] += int(keys[:, 3].sum())
+        T = torch.ones((n, 3), dtype=torch.float32, device=cuda)
+        background = torch.tensor(list(cam.background), dtype=torch.float32, device=cuda)
+        path = torch.arange(n, device=cuda)        # the row of L each record adds to
+        alive = torch.ones(n, dtype=torch.bool, device=cuda)
+        flags = rtx.RTX_SHADE_COUNTERS if counters else 0
+        for _ in range(cam.max_depth):
+            m = rays.shape[0]
+            if counters:
+                work["segments"] += int(alive.sum())
+            dev.trace_device(rays.data_ptr(), m, hits.data_ptr(), rtx.RTX_TRACE_UV, stream)
+            st = dev.shade_device(seed, rays.data_ptr(), hits.data_ptr(), keys.data_ptr(), m, bounce.data_ptr(), flags,
+                                  stream, stats=counters)
+            if counters:
+                work["hits"] += st.hits
+                work["rng_draws"] += st.rng_draws
+                work["texel_fetches"] += st.texel_fetches
+            b = bounce[:m]
+            bits = b.view(torch.int32)[:, 3]
+            hit = alive & (hits[:m, 1] != _MISS)
+            miss = alive & ~hit
+            emits = hit & ((bits & rtx.RTX_BOUNCE_EMITS) != 0)
+            alive = hit & ((bits & rtx.RTX_BOUNCE_SCATTERED) != 0)
+            L[path[miss]] = L[path[miss]] + T[miss] * background          # ray.go:52
+            L[path[emits]] = L[path[emits]] + T[emits] * b[emits, 4:7]    # ray.go:41, 47
+            if compact:
+                if not bool(alive.any()):
+                    break
+                T = T[alive] * b[alive, 0:3]                              # ray.go:47-50
+                rays, keys, path = b[alive, 8:16].contiguous(), keys[alive].contiguous(), path[alive]
+                alive = torch.ones(rays.shape[0], dtype=torch.bool, device=cuda)
+            else:
+                T = torch.where(alive[:, None], T * b[:, 0:3], T)
+                rays = b[:, 8:16].contiguous()  # an ended path's bounce ray is all zero: a miss from now on
+            keys[:, 2] += 1  # the next scatter's event
+    # camera.go:254-263: the samples summed in k order, times float32(1 / spp)
+    per_sample = L.view(spp, rows * width, 3)
+    total = torch.zeros((rows * width, 3), dtype=torch.float32, device=cuda)
+    for k in range(spp):
+        total = total + per_sample[k]
+    one = torch.ones((), dtype=torch.float32, device=cuda)
+    image = (total * (one / float(spp))).view(rows, width, 3)
+    return (image, work) if counters else image
