@@ -736,6 +736,159 @@ func (c *Camera) RenderProgressive(world Hittable, writer io.Writer, passSamples
 	return err
 }
 
+// Guide is one pixel of the first-hit guide images (rtx_guide, rtx.h "denoised previews"): the mean over a range of
+// samples of the albedo, the normal and the depth at the first hit of the render's own camera ray; Cover is the share
+// of the samples that hit anything, and Depth is 0 where none did.
+type Guide struct {
+	Albedo Vec3
+	Cover  float32
+	Normal Vec3
+	Depth  float32
+}
+
+// DenoiseParams are the preview filter's (rtx_denoise_params); DefaultDenoiseParams returns rtx_denoise_defaults'.
+type DenoiseParams struct {
+	Iterations                             uint32
+	SigmaNormal, SigmaDepth, SigmaLuminance float32
+}
+
+func DefaultDenoiseParams() DenoiseParams {
+	var p C.rtx_denoise_params
+	C.rtx_denoise_defaults(&p)
+	return DenoiseParams{Iterations: uint32(p.iterations), SigmaNormal: float32(p.sigma_normal),
+		SigmaDepth: float32(p.sigma_depth), SigmaLuminance: float32(p.sigma_luminance)}
+}
+
+func (p DenoiseParams) c() C.rtx_denoise_params {
+	return C.rtx_denoise_params{iterations: C.uint32_t(p.Iterations), sigma_normal: C.float(p.SigmaNormal),
+		sigma_depth: C.float(p.SigmaDepth), sigma_luminance: C.float(p.SigmaLuminance)}
+}
+
+// GuideImages is the first hit of GetRay (camera.go:265-299) for every pixel on the GPU, averaged over samples
+// [firstSample, firstSample + count) (rtx_guides): guides[y * W + x] belongs to pixel (x, y).  The world is
+// flattened and uploaded for the call, as in HitBatch.
+func (c *Camera) GuideImages(world Hittable, seed uint64, firstSample, count uint32) ([]Guide, error) {
+	c.init()
+	cam := c.gpuCamera()
+	region := C.rtx_region{x0: 0, y0: 0, width: cam.image_width, height: cam.image_height, rank: 0, world: 1, stripe: 0}
+	n := int(cam.image_width) * int(cam.image_height)
+	out := make([]Guide, n)
+	if n == 0 {
+		return out, nil
+	}
+	scene, err := sceneOf(world, seed)
+	if errors.Is(err, errUnsupported) {
+		return nil, errFallback
+	}
+	if err != nil {
+		return nil, err
+	}
+	defer C.rtx_scene_destroy(scene)
+	buf, ptr := alignedBytes(uintptr(n) * unsafe.Sizeof(C.rtx_guide{}))
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pin.Pin(&buf[0])
+	guides := (*C.rtx_guide)(ptr)
+	if rc := C.rtx_guides(scene, &cam, C.uint64_t(seed), &region, C.uint32_t(firstSample), C.uint32_t(count), guides, nil); rc != 0 {
+		if gpuMissing(rc) {
+			return nil, errFallback
+		}
+		return nil, rtxErr(rc)
+	}
+	v3 := func(a [3]C.float) Vec3 { return NewVec3(float32(a[0]), float32(a[1]), float32(a[2])) }
+	for i, rec := range unsafe.Slice(guides, n) {
+		var g C.rtx_guide = rec
+		out[i] = Guide{Albedo: v3(g.albedo), Cover: float32(g.cover), Normal: v3(g.normal), Depth: float32(g.depth)}
+	}
+	return out, nil
+}
+
+// Denoise is the preview filter (rtx_denoise) on the GPU: rgb and variance are a resolved width x rows image and the
+// variance of its mean, three float32 per pixel; guides are GuideImages' of the same pixels.  It returns the
+// filtered image.
+func Denoise(rgb, variance []float32, guides []Guide, width, rows int, p DenoiseParams) ([]float32, error) {
+	n := width * rows
+	if width < 0 || rows < 0 || len(rgb) != 3*n || len(variance) != 3*n || len(guides) != n {
+		return nil, errors.New("rtx: Denoise needs three colour and variance values and one guide per pixel")
+	}
+	out := make([]float32, 3*n)
+	if n == 0 {
+		return out, nil
+	}
+	buf, ptr := alignedBytes(uintptr(n) * unsafe.Sizeof(C.rtx_guide{}))
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pin.Pin(&buf[0])
+	pin.Pin(&rgb[0])
+	pin.Pin(&variance[0])
+	pin.Pin(&out[0])
+	cguides := (*C.rtx_guide)(ptr)
+	records := unsafe.Slice(cguides, n)
+	for i := range records {
+		records[i] = C.rtx_guide{albedo: vec(guides[i].Albedo), cover: C.float(guides[i].Cover),
+			normal: vec(guides[i].Normal), depth: C.float(guides[i].Depth)}
+	}
+	prm := p.c()
+	if rc := C.rtx_denoise((*C.float)(unsafe.Pointer(&rgb[0])), (*C.float)(unsafe.Pointer(&variance[0])), cguides, C.uint32_t(width), C.uint32_t(rows), &prm, (*C.float)(unsafe.Pointer(&out[0]))); rc != 0 {
+		if gpuMissing(rc) {
+			return nil, errFallback
+		}
+		return nil, rtxErr(rc)
+	}
+	return out, nil
+}
+
+// RenderPreviews is RenderProgressive with a denoised preview after every pass (rtx_accum_preview_ppm): onPreview is
+// handed the samples done and the P3 bytes of the filtered image so far, steered by guides over the first
+// min(done, guideSamples) samples, and returning false stops the render there.  The bytes written to writer at the
+// end are the undenoised image's, exactly RenderProgressive's: a preview is a separate output and changes no render.
+func (c *Camera) RenderPreviews(world Hittable, writer io.Writer, passSamples, guideSamples int, p DenoiseParams, onPreview func(done int, ppm []byte) bool) error {
+	c.init()
+	cfg := c.gpuConfig()
+	if passSamples <= 0 {
+		passSamples = c.samplesPerPixel
+	}
+	scene, err := sceneOf(world, cfg.seed)
+	if err != nil {
+		return err
+	}
+	defer C.rtx_scene_destroy(scene) // (deferred calls run last in, first out: the accumulator goes first)
+	cam := c.gpuCamera()
+	region := C.rtx_region{x0: 0, y0: 0, width: cam.image_width, height: cam.image_height, rank: 0, world: 1, stripe: 0}
+	var acc *C.rtx_accum
+	if rc := C.rtx_accum_create(scene, &cam, C.uint64_t(cfg.seed), &region, &acc); rc != 0 {
+		return rtxErr(rc)
+	}
+	defer C.rtx_accum_destroy(acc)
+	prm := p.c()
+	text := make([]byte, int(C.rtx_ppm_max_bytes(cam.image_width, cam.image_height)))
+	var n C.uint64_t
+	for done := 0; done < c.samplesPerPixel; {
+		count := min(passSamples, c.samplesPerPixel-done)
+		if rc := C.rtx_accum_add(acc, C.uint32_t(count), nil, 0, nil); rc != 0 {
+			return rtxErr(rc)
+		}
+		done = int(C.rtx_accum_samples(acc))
+		if onPreview == nil {
+			continue
+		}
+		if rc := C.rtx_accum_preview_ppm(acc, C.uint32_t(guideSamples), &prm, (*C.char)(unsafe.Pointer(&text[0])), C.uint64_t(len(text)), &n); rc != 0 {
+			return rtxErr(rc)
+		}
+		if !onPreview(done, text[:int(n)]) {
+			break
+		}
+	}
+	if rc := C.rtx_accum_ppm(acc, (*C.char)(unsafe.Pointer(&text[0])), C.uint64_t(len(text)), &n); rc != 0 {
+		return rtxErr(rc)
+	}
+	if rc := C.rtx_device_check(0); rc != 0 { // the passes ran without stats: the sticky error word, once
+		return rtxErr(rc)
+	}
+	_, err = writer.Write(text[:int(n)])
+	return err
+}
+
 // renderOnDevices renders on `gpus` devices and writes Render's P3 bytes; errFallback when the GPU
 // path cannot carry the render (nothing has been written then).
 func (c *Camera) renderOnDevices(world Hittable, writer io.Writer, seed uint64, gpus int) error {

@@ -734,6 +734,117 @@ int rtx_shade_device(rtx_scene* scene, uint64_t seed, const rtx_ray* d_rays, con
 int rtx_shade(rtx_scene* scene, uint64_t seed, const rtx_ray* rays, const rtx_hit* hits, const rtx_path_key* keys,
               uint64_t n, rtx_bounce* out, uint32_t flags, rtx_shade_stats* stats);
 
+/* ---- denoised previews (ABI 10, additive) -------------------------
+ * The first resolved image of a progressive render is noise.  A preview is that image passed through a
+ * variance-guided, edge-avoiding a-trous filter steered by first-hit guide images.  It is a SEPARATE output: no
+ * render, no resolve and no image the oracle checks changes.
+ *
+ * Guide images.  One rtx_guide per pixel of the region's shard, row-major in the compacted shard rows
+ * rtx_render_region_device writes (rtx_region): the mean, over samples k = first_sample .. first_sample + count - 1,
+ * of the first hit of the render's own camera ray for (pixel, k): event 0 of DESIGN.md §3, the ray rtx_camera_rays
+ * produces for that pixel and sample, lens included.  Per sample:
+ *   a miss:  a = (1, 1, 1), n = 0, no depth;
+ *   a hit:   n = HitInfo.normal (unit, flipped against the ray), t = HitInfo.t (the camera's rays end on the focus
+ *            plane, so t is planar depth in units of the focus distance), and a = the Lambertian's texture value at
+ *            (u, v, point) (all four texture kinds), the Metal's albedo, (1, 1, 1) for Dielectric and DiffuseLight.
+ * The fold is float32 in k order, each operation rounded, no fused multiply-add:
+ *   A = A + a;  N = N + n;  on a hit  Z = Z + t;  c = c + 1
+ *   inv = 1.0f / (float)count;  albedo = A * inv;  normal = N * inv;  cover = (float)c * inv
+ *   depth = c ? Z / (float)c : 0
+ * So a guide equals rtx_camera_rays -> rtx_trace(RTX_TRACE_UV) -> rtx_shade folded this way, bit for bit on a scene
+ * that keeps the caller's tree (on the library's own trees up to the grazing hits of DESIGN.md §12), without the
+ * 32 + 48 + 64 B per sample those calls move through memory. */
+typedef struct rtx_guide { /* 32 B */
+    float albedo[3];
+    float cover;    /* the share of the samples that hit something */
+    float normal[3];
+    float depth;    /* mean t of the samples that hit; 0 when none did */
+} rtx_guide;
+typedef struct rtx_guide_stats {
+    uint64_t rays;    /* pixels * count */
+    double kernel_ms; /* device time of the launch, HIP events on the stream */
+} rtx_guide_stats;
+
+/* Guides of the region's shard into device memory of the CURRENT device, on the given HIP stream.  Returns after
+ * enqueueing unless stats != NULL; then it synchronises the stream and fills stats.  count == 0 (a mean over
+ * nothing), first_sample + count past 2^32 - 1, a NULL scene, cam, region or d_guides, a d_guides not aligned to
+ * 16 B (all checked before any device is touched) and a current device that holds no copy of the scene return
+ * RTX_ERR_INVALID_ARG; the camera and the region are validated as by rtx_render_region_device.  An empty shard
+ * returns RTX_OK and launches nothing.  The call takes the scene's mutex and walks the ray queries' layouts (hinted
+ * with rtx_camera_octant(cam)); it uses none of the sample scratch and no render's counters, so a call between two
+ * renders changes neither. */
+int rtx_guides_device(rtx_scene* scene, const rtx_camera* cam, uint64_t seed, const rtx_region* region,
+                      uint32_t first_sample, uint32_t count, rtx_guide* d_guides, void* hip_stream,
+                      rtx_guide_stats* stats);
+/* The same into host memory, on the current device.  Blocking. */
+int rtx_guides(rtx_scene* scene, const rtx_camera* cam, uint64_t seed, const rtx_region* region, uint32_t first_sample,
+               uint32_t count, rtx_guide* guides, rtx_guide_stats* stats);
+
+/* The filter.  d_rgb and d_var are the images rtx_accum_resolve_device writes (width x rows, 3 floats per pixel;
+ * d_var the variance of the mean, required), d_guides the guides of the same pixels, d_out the filtered image
+ * (3 floats per pixel).  Stateless: no scene, no lock, like rtx_encode_ppm_device.  The arithmetic is the contract:
+ * float32, every operation rounded on its own, no fused multiply-add, no square root, no exp.
+ *
+ *   prepare, per pixel:   a_c = albedo_c > 0.01f ? albedo_c : 0.01f;   c_c = rgb_c / a_c
+ *                         v = (var_r / (a_r * a_r) + var_g / (a_g * a_g)) + var_b / (a_b * a_b)
+ *   level i = 0 .. iterations - 1, s = 1 << i, (c, v) -> (c', v'), n = guide.normal, z = guide.depth:
+ *     vb = SV / SK, both sums starting at 0 over the taps p + (a, b) inside the image, b = -1..1 outer, a = -1..1
+ *          inner:  k = k3[b + 1] * k3[a + 1], k3 = (1, 2, 1);  SV = SV + k * v;  SK = SK + k
+ *     l_p = (c_r + c_g) + c_b;    dl = (sigma_luminance * sigma_luminance) * vb + 1e-6f
+ *     W = C_c = V = 0;  for dy = -2..2, for dx = -2..2, q = p + s * (dx, dy), taps outside the image skipped:
+ *         dn = n_p - n_q;  xn = ((dn_x * dn_x + dn_y * dn_y) + dn_z * dn_z) / (sigma_normal * sigma_normal)
+ *         m = (float)(s * max(|dx|, |dy|));  zm = z_p > z_q ? z_p : z_q;  tz = (sigma_depth * m) * zm
+ *         dz = z_p - z_q;  xz = (dz * dz) / (tz * tz + 1e-6f)
+ *         d = l_p - l_q;   xl = (d * d) / dl
+ *         w = (((k5[dy + 2] * k5[dx + 2]) * f(xn)) * f(xz)) * f(xl),  k5 = (1/16, 1/4, 3/8, 1/4, 1/16),
+ *                                                                    f(x) = 1 - x > 0 ? 1 - x : 0
+ *         if (w > 0) { W = W + w;  C_c = C_c + w * c_q;  V = V + (w * w) * v_q }
+ *     c' = C / W;   v' = V / (W * W)
+ *   finish:  out_c = c_c * a_c
+ *
+ * Sky next to sky has dn = 0 and dz = 0: weight k5 * k5; sky next to geometry has |dn|^2 = 1 > sigma_normal^2:
+ * weight 0.  A NaN colour (resolve gives it variance 0) weighs 0 in every neighbour's sum and comes out NaN itself;
+ * from the second level on its variance is NaN too, which the 3 x 3 variance sum hands to the pixels around it, so
+ * after i levels the pixels within i - 1 of it are NaN.
+ * sigma_depth is the relative depth slope tolerated per pixel of distance, so it scales with the resolution: a
+ * surface seen at twice the pixel count changes half as much per pixel.
+ * iterations is 1 to 6; sigma_normal > 0, sigma_depth >= 0, sigma_luminance >= 0.  Every pointer is aligned to
+ * 16 B; d_work holds at least rtx_denoise_workspace_bytes(width, rows); d_out overlaps neither an input nor d_work,
+ * and d_work no input.  A violation of any of these, or a NULL pointer, returns RTX_ERR_INVALID_ARG before any
+ * device is touched.  width * rows == 0 returns RTX_OK and launches nothing.  Returns after enqueueing
+ * iterations + 1 kernels on the stream. */
+typedef struct rtx_denoise_params {
+    uint32_t iterations;
+    float sigma_normal;
+    float sigma_depth;
+    float sigma_luminance;
+} rtx_denoise_params;
+/* 5, 0.45f, 0.05f, 8.0f */
+void rtx_denoise_defaults(rtx_denoise_params* params);
+/* Two float4 images: 32 B per pixel. */
+uint64_t rtx_denoise_workspace_bytes(uint32_t width, uint32_t rows);
+int rtx_denoise_device(const float* d_rgb, const float* d_var, const rtx_guide* d_guides, uint32_t width, uint32_t rows,
+                       const rtx_denoise_params* params, float* d_out, void* d_work, uint64_t work_bytes,
+                       void* hip_stream);
+/* The same for images in host memory (no alignment rule, no workspace), on the current device.  Blocking. */
+int rtx_denoise(const float* rgb, const float* var, const rtx_guide* guides, uint32_t width, uint32_t rows,
+                const rtx_denoise_params* params, float* out_rgb);
+
+/* A preview of an accumulator after n >= 1 samples, into device memory d_out (the region's compacted shard rows,
+ * 3 floats per pixel, aligned to 16 B) on hip_stream:  rtx_accum_resolve_device, rtx_guides_device over samples
+ * [0, min(n, guide_samples)), rtx_denoise_device; its bytes are those of the three calls composed.  params NULL:
+ * rtx_denoise_defaults.  guide_samples == 0 returns RTX_ERR_INVALID_ARG.  The resolved image, its variance, the
+ * guides and the filter's workspace (88 B per pixel) belong to the accumulator: allocated by its first preview
+ * (a blocking allocation), freed with it, not part of the per-device scratch and not counted by
+ * rtx_device_scratch_bytes.  S, Q and n are not modified: more passes may follow.  Returns after enqueueing. */
+int rtx_accum_preview_device(rtx_accum* accum, uint32_t guide_samples, const rtx_denoise_params* params, float* d_out,
+                             void* hip_stream);
+/* The same into host memory, after every render enqueued on the device so far.  Blocking. */
+int rtx_accum_preview(rtx_accum* accum, uint32_t guide_samples, const rtx_denoise_params* params, float* out_rgb);
+/* The preview encoded as rtx_accum_ppm encodes the resolved image.  Blocking. */
+int rtx_accum_preview_ppm(rtx_accum* accum, uint32_t guide_samples, const rtx_denoise_params* params, char* out_text,
+                          uint64_t capacity, uint64_t* out_len);
+
 #ifdef __cplusplus
 }
 #endif

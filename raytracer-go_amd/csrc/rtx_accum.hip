@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <new>
 
+#include "rtx_guides.h"
 #include "rtx_internal.h"
 #include "rtx_ppm.h"
 
@@ -21,6 +22,9 @@ struct rtx_accum {
     uint64_t slots = 0;        // tiles x 64
     rtxd::DeviceBuffer sums;   // S: slots x 3 floats, then Q's slots x 3
     rtxd::DeviceBuffer noisy;  // resolve_accum's count (one u64)
+    // previews, made by the first one: the resolved image, its variance, the guides and the filter's
+    // workspace, 12 + 12 + 32 + 32 B per pixel of the shard
+    rtxd::DeviceBuffer preview;
     uint32_t n = 0;
     float* s() const { return sums.as<float>(); }
     float* q() const { return s() + slots * 3; }
@@ -50,6 +54,37 @@ int accum_resolve_locked(rtx_accum* a, float* d_rgb, float* d_var, float rel_tol
         *noisy = h;
     }
     return RTX_OK;
+}
+
+// The checks of the three preview entries that need no device.
+int check_preview(const rtx_accum* a, uint32_t guide_samples, const rtx_denoise_params** params, rtx_denoise_params* dflt) {
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    if (guide_samples == 0) return fail(RTX_ERR_INVALID_ARG, "guides over 0 samples (a mean over nothing)");
+    if (a->n == 0) return fail(RTX_ERR_INVALID_ARG, "nothing accumulated yet");
+    if (!*params) {
+        rtx_denoise_defaults(dflt);
+        *params = dflt;
+    }
+    return RTX_OK;
+}
+
+// rtx_accum_preview_device with a->scene->mu held: resolve, guides over [0, min(n, guide_samples)), filter.
+int accum_preview_locked(rtx_accum* a, uint32_t guide_samples, const rtx_denoise_params* params, float* d_out, hipStream_t st) {
+    const uint64_t P = (uint64_t)a->rows * a->region.width;
+    if (P == 0) return RTX_OK;
+    // the four images, each starting on a 16-B boundary
+    const size_t img = ((size_t)P * 3 * sizeof(float) + 15) / 16 * 16, gb = (size_t)P * sizeof(rtx_guide);
+    const uint64_t wb = rtx_denoise_workspace_bytes(a->region.width, a->rows);
+    HIP_TRY(a->preview.reserve(2 * img + gb + (size_t)wb));
+    char* base = a->preview.as<char>();
+    float* rgb = reinterpret_cast<float*>(base);
+    float* var = reinterpret_cast<float*>(base + img);
+    rtx_guide* guides = reinterpret_cast<rtx_guide*>(base + 2 * img);
+    void* work = base + 2 * img + gb;
+    if (int rc = accum_resolve_locked(a, rgb, var, 0.0f, st, nullptr)) return rc;
+    if (int rc = guides_locked(a->scene, &a->cam, a->seed, &a->region, 0, std::min(a->n, guide_samples), guides, st, nullptr))
+        return rc;
+    return rtx_denoise_device(rgb, var, guides, a->region.width, a->rows, params, d_out, work, wb, st);
 }
 }  // namespace
 
@@ -167,6 +202,59 @@ int rtx_accum_ppm(rtx_accum* a, char* out_text, uint64_t capacity, uint64_t* out
     return ppm_to_host(rc, rgb, W, H, text, st, out_text, capacity, out_len);
 }
 
+int rtx_accum_preview_device(rtx_accum* a, uint32_t guide_samples, const rtx_denoise_params* params, float* d_out,
+                             void* hip_stream) {
+    g_last_error.clear();
+    rtx_denoise_params dflt;
+    if (int rc = check_preview(a, guide_samples, &params, &dflt)) return rc;
+    if (!d_out && (uint64_t)a->rows * a->region.width) return fail(RTX_ERR_INVALID_ARG, "NULL output");
+    if (int rc = accum_device(a)) return rc;
+    std::lock_guard<std::mutex> lk(a->scene->mu);
+    return accum_preview_locked(a, guide_samples, params, d_out, (hipStream_t)hip_stream);
+}
+
+int rtx_accum_preview(rtx_accum* a, uint32_t guide_samples, const rtx_denoise_params* params, float* out_rgb) {
+    g_last_error.clear();
+    rtx_denoise_params dflt;
+    if (int rc = check_preview(a, guide_samples, &params, &dflt)) return rc;
+    const size_t bytes = (size_t)a->rows * a->region.width * 3 * sizeof(float);
+    if (!out_rgb && bytes) return fail(RTX_ERR_INVALID_ARG, "NULL output");
+    if (int rc = accum_device(a)) return rc;
+    std::lock_guard<std::mutex> lk(a->scene->mu);
+    std::lock_guard<std::mutex> bl(g_render_mu);  // the cached image buffer and stream
+    hipStream_t st = render_stream(a->device);
+    float* rgb = static_cast<float*>(render_buffer(a->device, -3, std::max<size_t>(1, bytes)));
+    if (!st) return fail(RTX_ERR_HIP, "stream on device %d", a->device);
+    if (!rgb) return fail(RTX_ERR_OOM, "device buffer for a %ux%u preview", a->region.width, a->rows);
+    if (int rc = wait_for_renders(a->device, st)) return rc;
+    int rc = accum_preview_locked(a, guide_samples, params, rgb, st);
+    if (rc == RTX_OK && bytes && copy_to_host(out_rgb, rgb, bytes, st) != hipSuccess)
+        rc = fail(RTX_ERR_HIP, "copying the preview to the host");
+    (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+int rtx_accum_preview_ppm(rtx_accum* a, uint32_t guide_samples, const rtx_denoise_params* params, char* out_text,
+                          uint64_t capacity, uint64_t* out_len) {
+    g_last_error.clear();
+    rtx_denoise_params dflt;
+    if (int rc = check_preview(a, guide_samples, &params, &dflt)) return rc;
+    if (!out_text || !out_len) return fail(RTX_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = accum_device(a)) return rc;
+    const uint32_t W = a->region.width, H = a->rows;
+    const uint64_t need = rtxd::ppm_max_bytes(W, H);
+    std::lock_guard<std::mutex> lk(a->scene->mu);
+    std::lock_guard<std::mutex> bl(g_render_mu);
+    hipStream_t st = render_stream(a->device);
+    float* rgb = static_cast<float*>(render_buffer(a->device, -3, std::max<size_t>(1, (size_t)W * H * 3 * sizeof(float))));
+    char* text = static_cast<char*>(render_buffer(a->device, -4, need));
+    if (!st) return fail(RTX_ERR_HIP, "stream on device %d", a->device);
+    if (!rgb || !text) return fail(RTX_ERR_OOM, "device buffers for a %ux%u PPM", W, H);
+    if (int rc = wait_for_renders(a->device, st)) return rc;
+    const int rc = accum_preview_locked(a, guide_samples, params, rgb, st);
+    return ppm_to_host(rc, rgb, W, H, text, st, out_text, capacity, out_len);
+}
+
 int rtx_accum_reset(rtx_accum* a) {
     g_last_error.clear();
     if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
@@ -186,6 +274,7 @@ void rtx_accum_destroy(rtx_accum* a) {
             (void)hipDeviceSynchronize();
             a->sums.release();
             a->noisy.release();
+            a->preview.release();
         }
     }
     delete a;

@@ -6,8 +6,9 @@
 //                      word, render buffers / streams / events, RCCL; rtx_release_device_memory, rtx_device_check
 //   rtx_render.hip     the scene's device copy and layouts, enqueue_on / collect_on, the region render, PPM
 //   rtx_bands.hip      rtx_render(_ex): the bands and their assembly
-//   rtx_accum.hip      progressive passes; rtx_trace_capi.hip: ray queries; rtx_shade_capi.hip: camera rays and
-//                      material scatter for a batch; rtx_capi.hip: scene create / destroy
+//   rtx_accum.hip      progressive passes and their previews; rtx_trace_capi.hip: ray queries; rtx_shade_capi.hip:
+//                      camera rays and material scatter for a batch; rtx_guides_capi.hip: guide images and the
+//                      preview filter; rtx_capi.hip: scene create / destroy
 //
 // A unit that defines RTX_HOST_ONLY before including this header sees the first half only, which names no HIP type:
 // it compiles with the plain host compiler and links without the runtime (tests/test_pack_layout.py).
@@ -223,6 +224,16 @@ int render_region_locked(rtx_scene* s, const rtx_camera* cam, uint64_t seed, con
 // fits; st is synchronised either way.
 int ppm_to_host(int rc, const float* rgb, uint32_t W, uint32_t H, char* text, hipStream_t st, char* out_text,
                 uint64_t capacity, uint64_t* out_len);
+
+// ---- rtx_trace_capi.hip --------------------------------------------------------------------------------------
+// What a trace on copy c needs beside the scene (s->mu held, current device = c's), made on first use; *out: the
+// trace layout for the hinted octant.
+int ensure_trace(rtx_scene* s, DeviceCopy* c, uint32_t oct, const DeviceLayout** out);
+
+// ---- rtx_guides_capi.hip -------------------------------------------------------------------------------------
+// rtx_guides_device after its checks, with s->mu held (rtx_accum_preview*).
+int guides_locked(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const rtx_region* region, uint32_t first_sample,
+                  uint32_t count, rtx_guide* d_guides, hipStream_t stream, rtx_guide_stats* stats);
 
 // ---- rtx_bands.hip -------------------------------------------------------------------------------------------
 int render_bands_locked(rtx_scene* s, const rtx_camera* cam, uint64_t seed, int n_gpus, uint32_t flags, float* out_rgb,

@@ -27,6 +27,10 @@ int check_trace(const rtx_scene* s, const void* rays, uint64_t n, const void* hi
     return RTX_OK;
 }
 
+}  // namespace
+
+namespace rtxh {
+
 // What a trace on copy c needs beside the scene (s->mu held, current device = c's), made on first use: the
 // rank table (the inverse of rank_spheres: one word per sphere entry of `base`, so every entry of a sphere referenced
 // more than once names it), the trace's counters and events, and the trace layout for `oct`: the rebuilt tree for
@@ -64,7 +68,7 @@ int ensure_trace(rtx_scene* s, DeviceCopy* c, uint32_t oct, const DeviceLayout**
     return RTX_OK;
 }
 
-}  // namespace
+}  // namespace rtxh
 
 extern "C" {
 

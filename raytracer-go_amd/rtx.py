@@ -167,9 +167,36 @@ class ShadeStats(ctypes.Structure):  # rtx_shade_stats
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class Guide(ctypes.Structure):  # rtx_guide, 32 B
+    _fields_ = [("albedo", c_float * 3), ("cover", c_float), ("normal", c_float * 3), ("depth", c_float)]
+
+
+class GuideStats(ctypes.Structure):  # rtx_guide_stats
+    _fields_ = [("rays", c_uint64), ("kernel_ms", c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class DenoiseParams(ctypes.Structure):  # rtx_denoise_params; DenoiseParams.defaults() = rtx_denoise_defaults
+    _fields_ = [("iterations", c_uint32), ("sigma_normal", c_float), ("sigma_depth", c_float),
+                ("sigma_luminance", c_float)]
+
+    @classmethod
+    def defaults(cls) -> "DenoiseParams":
+        p = cls()
+        load().rtx_denoise_defaults(ctypes.byref(p))
+        return p
+
+
 def __getattr__(name: str):
-    """RAY_DTYPE / HIT_DTYPE / KEY_DTYPE / BOUNCE_DTYPE: the numpy structured dtypes of rtx_ray, rtx_hit, rtx_path_key
-    and rtx_bounce (numpy is imported on first use, as everywhere in this module)."""
+    """RAY_DTYPE / HIT_DTYPE / KEY_DTYPE / BOUNCE_DTYPE / GUIDE_DTYPE: the numpy structured dtypes of rtx_ray, rtx_hit,
+    rtx_path_key, rtx_bounce and rtx_guide (numpy is imported on first use, as everywhere in this module)."""
+    if name == "GUIDE_DTYPE":
+        import numpy as np
+        globals().update(GUIDE_DTYPE=np.dtype([("albedo", "<f4", (3,)), ("cover", "<f4"), ("normal", "<f4", (3,)),
+                                               ("depth", "<f4")]))
+        return globals()[name]
     if name in ("RAY_DTYPE", "HIT_DTYPE", "KEY_DTYPE", "BOUNCE_DTYPE"):
         import numpy as np
         ray = np.dtype([("origin", "<f4", (3,)), ("tmin", "<f4"), ("dir", "<f4", (3,)), ("tmax", "<f4")])
@@ -198,6 +225,9 @@ RTX_SYMBOLS = [
     "rtx_trace_device", "rtx_trace",
     # path building blocks (ABI 10, additive)
     "rtx_camera_rays_device", "rtx_camera_rays", "rtx_shade_device", "rtx_shade",
+    # denoised previews (ABI 10, additive)
+    "rtx_guides_device", "rtx_guides", "rtx_denoise_defaults", "rtx_denoise_workspace_bytes", "rtx_denoise_device",
+    "rtx_denoise", "rtx_accum_preview_device", "rtx_accum_preview", "rtx_accum_preview_ppm",
 ]
 RTXHOST_SYMBOLS = [
     "rtxhost_build_scene", "rtxhost_scene_free", "rtxhost_scene_desc", "rtxhost_scene_camera",
@@ -327,6 +357,29 @@ def load() -> ctypes.CDLL:
         L.rtx_shade.argtypes = [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32,
                                 POINTER(ShadeStats)]
         L.rtx_shade.restype = c_int
+    if hasattr(L, "rtx_guides_device"):  # ABI 10, additive (RTX_LIB may name an older build for A/B)
+        L.rtx_guides_device.argtypes = [c_void_p, POINTER(Camera), c_uint64, POINTER(Region), c_uint32, c_uint32, c_void_p,
+                                        c_void_p, POINTER(GuideStats)]
+        L.rtx_guides_device.restype = c_int
+        L.rtx_guides.argtypes = [c_void_p, POINTER(Camera), c_uint64, POINTER(Region), c_uint32, c_uint32, c_void_p,
+                                 POINTER(GuideStats)]
+        L.rtx_guides.restype = c_int
+        L.rtx_denoise_defaults.argtypes = [POINTER(DenoiseParams)]
+        L.rtx_denoise_defaults.restype = None
+        L.rtx_denoise_workspace_bytes.argtypes = [c_uint32, c_uint32]
+        L.rtx_denoise_workspace_bytes.restype = c_uint64
+        L.rtx_denoise_device.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, POINTER(DenoiseParams), c_void_p,
+                                         c_void_p, c_uint64, c_void_p]
+        L.rtx_denoise_device.restype = c_int
+        L.rtx_denoise.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, POINTER(DenoiseParams), c_void_p]
+        L.rtx_denoise.restype = c_int
+        L.rtx_accum_preview_device.argtypes = [c_void_p, c_uint32, POINTER(DenoiseParams), c_void_p, c_void_p]
+        L.rtx_accum_preview_device.restype = c_int
+        L.rtx_accum_preview.argtypes = [c_void_p, c_uint32, POINTER(DenoiseParams), c_void_p]
+        L.rtx_accum_preview.restype = c_int
+        L.rtx_accum_preview_ppm.argtypes = [c_void_p, c_uint32, POINTER(DenoiseParams), c_void_p, c_uint64,
+                                            POINTER(c_uint64)]
+        L.rtx_accum_preview_ppm.restype = c_int
     _lib = L
     return L
 
@@ -639,6 +692,30 @@ class DeviceScene:
         out = out.reshape(arrs[0].shape)
         return (out, st) if stats else out
 
+    def guides_device(self, cam: Camera, seed: int, region: Region, first: int, count: int, guides_ptr: int,
+                      stream: int = 0, stats: bool = False):
+        """rtx_guides_device: the first-hit guides (rtx_guide, 32 B per pixel of the region's shard, 16-B aligned) of
+        samples [first, first + count) into device memory of the current device.  Enqueues and returns None, or with
+        stats=True waits and returns the GuideStats."""
+        st = GuideStats() if stats else None
+        check(load().rtx_guides_device(self._h, ctypes.byref(cam), seed, ctypes.byref(region), first, count,
+                                       c_void_p(guides_ptr), c_void_p(stream),
+                                       ctypes.byref(st) if st is not None else None), "rtx_guides_device")
+        return st
+
+    def guides(self, cam: Camera, seed: int, region: Region, first: int = 0, count=None, stats: bool = False):
+        """rtx_guides: an array of GUIDE_DTYPE of shape (rows, width) (and the GuideStats with stats=True); count
+        defaults to the camera's samples_per_pixel.  Blocking."""
+        if count is None:
+            count = cam.samples_per_pixel
+        rows = region_rows(region)
+        out = _aligned_empty(rows * region.width, __getattr__("GUIDE_DTYPE"))
+        st = GuideStats() if stats else None
+        check(load().rtx_guides(self._h, ctypes.byref(cam), seed, ctypes.byref(region), first, count,
+                                out.ctypes.data_as(c_void_p), ctypes.byref(st) if st is not None else None), "rtx_guides")
+        out = out.reshape(rows, region.width)
+        return (out, st) if stats else out
+
     def accumulator(self, cam: Camera, seed: int, region: Region) -> "Accumulator":
         """rtx_accum_create on the current device: progressive passes over `region` (close it before the scene)."""
         return Accumulator(self, cam, seed, region)
@@ -710,6 +787,31 @@ class Accumulator:
         check(L.rtx_accum_ppm(self._h, buf.ctypes.data_as(c_void_p), cap, ctypes.byref(n)), "rtx_accum_ppm")
         return buf[: n.value].tobytes()
 
+    def preview_device(self, out_ptr: int, guide_samples: int = 4, params: "DenoiseParams" = None, stream: int = 0) -> None:
+        """rtx_accum_preview_device: the denoised image so far (3 floats per pixel, 16-B aligned) into device memory:
+        resolve, guides over the first min(n, guide_samples) samples, filter (params None: the defaults).  Enqueues."""
+        check(load().rtx_accum_preview_device(self._h, guide_samples, ctypes.byref(params) if params is not None else None,
+                                              c_void_p(out_ptr), c_void_p(stream)), "rtx_accum_preview_device")
+
+    def preview(self, guide_samples: int = 4, params: "DenoiseParams" = None):
+        """rtx_accum_preview: float32 [rows, width, 3], the denoised image so far.  Blocking."""
+        import numpy as np
+        rgb = np.zeros((self.rows, self.width, 3), dtype=np.float32)
+        check(load().rtx_accum_preview(self._h, guide_samples, ctypes.byref(params) if params is not None else None,
+                                       rgb.ctypes.data_as(c_void_p)), "rtx_accum_preview")
+        return rgb
+
+    def preview_ppm(self, guide_samples: int = 4, params: "DenoiseParams" = None) -> bytes:
+        """rtx_accum_preview_ppm: the P3 bytes of the denoised image so far."""
+        import numpy as np
+        L = load()
+        cap = int(L.rtx_ppm_max_bytes(self.width, self.rows))
+        buf = np.empty(cap, dtype=np.uint8)
+        n = c_uint64()
+        check(L.rtx_accum_preview_ppm(self._h, guide_samples, ctypes.byref(params) if params is not None else None,
+                                      buf.ctypes.data_as(c_void_p), cap, ctypes.byref(n)), "rtx_accum_preview_ppm")
+        return buf[: n.value].tobytes()
+
     def reset(self) -> None:
         check(load().rtx_accum_reset(self._h), "rtx_accum_reset")
 
@@ -755,6 +857,41 @@ def camera_rays(cam: Camera, seed: int, region: Region, first: int = 0, count=No
                                  rays.ctypes.data_as(c_void_p), keys.ctypes.data_as(c_void_p)), "rtx_camera_rays")
     shape = (count, rows, region.width)
     return rays.reshape(shape), keys.reshape(shape)
+
+
+def denoise_workspace_bytes(width: int, rows: int) -> int:
+    """rtx_denoise_workspace_bytes: the bytes of workspace rtx_denoise_device needs for a width x rows image."""
+    return int(load().rtx_denoise_workspace_bytes(width, rows))
+
+
+def denoise_device(rgb_ptr: int, var_ptr: int, guides_ptr: int, width: int, rows: int, out_ptr: int, work_ptr: int,
+                   work_bytes: int, params: "DenoiseParams" = None, stream: int = 0) -> None:
+    """rtx_denoise_device: the edge-avoiding filter of a resolved image (rgb, var: 3 floats per pixel; guides: rtx_guide)
+    into out, device memory of the current device, every pointer 16-B aligned (params None: the defaults).  Enqueues."""
+    if params is None:
+        params = DenoiseParams.defaults()
+    check(load().rtx_denoise_device(c_void_p(rgb_ptr), c_void_p(var_ptr), c_void_p(guides_ptr), width, rows,
+                                    ctypes.byref(params), c_void_p(out_ptr), c_void_p(work_ptr), work_bytes,
+                                    c_void_p(stream)), "rtx_denoise_device")
+
+
+def denoise(rgb, var, guides, params: "DenoiseParams" = None):
+    """rtx_denoise: float32 [rows, width, 3] rgb and var and a [rows, width] array of GUIDE_DTYPE in, the filtered
+    float32 [rows, width, 3] image out.  Blocking."""
+    import numpy as np
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    var = np.ascontiguousarray(var, dtype=np.float32)
+    guides = np.ascontiguousarray(guides)
+    if guides.dtype != __getattr__("GUIDE_DTYPE"):
+        raise TypeError(f"guides must have dtype rtx.GUIDE_DTYPE, not {guides.dtype}")
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or var.shape != rgb.shape or guides.shape != rgb.shape[:2]:
+        raise ValueError("rgb and var must be [rows, width, 3] and guides [rows, width]")
+    if params is None:
+        params = DenoiseParams.defaults()
+    out = np.zeros_like(rgb)
+    check(load().rtx_denoise(rgb.ctypes.data_as(c_void_p), var.ctypes.data_as(c_void_p), guides.ctypes.data_as(c_void_p),
+                             rgb.shape[1], rgb.shape[0], ctypes.byref(params), out.ctypes.data_as(c_void_p)), "rtx_denoise")
+    return out
 
 
 def release_device_memory(device: int = -1) -> None:
