@@ -736,6 +736,58 @@ func (c *Camera) RenderProgressive(world Hittable, writer io.Writer, passSamples
 	return err
 }
 
+// RenderAdaptive is RenderProgressive with adaptive passes (rtx_accum_add_adaptive, rtx.h "adaptive sampling"): before
+// every pass the 64-pixel tiles none of whose pixels is noisy at relTol are closed (once minSamples have been offered),
+// and the pass samples the others only.  It ends when a pass found no open tile or at samplesPerPixel offered, and
+// writes the P3 bytes of the image: every pixel the mean of the samples it received, bit for bit that pixel of a
+// Render at as many samples.  onPass (when not nil) is told the samples offered and the tiles and pixels the pass
+// sampled; returning false stops the render there.  Stopping on an estimate biases the image (a tile that has not seen
+// its first bright sample closes early): minSamples is the guard.
+func (c *Camera) RenderAdaptive(world Hittable, writer io.Writer, passSamples int, relTol float32, minSamples int, onPass func(offered int, openTiles, openPixels uint64) bool) error {
+	c.init()
+	cfg := c.gpuConfig()
+	if passSamples <= 0 {
+		passSamples = c.samplesPerPixel
+	}
+	scene, err := sceneOf(world, cfg.seed)
+	if err != nil {
+		return err
+	}
+	defer C.rtx_scene_destroy(scene)
+	cam := c.gpuCamera()
+	region := C.rtx_region{x0: 0, y0: 0, width: cam.image_width, height: cam.image_height, rank: 0, world: 1, stripe: 0}
+	var acc *C.rtx_accum
+	if rc := C.rtx_accum_create(scene, &cam, C.uint64_t(cfg.seed), &region, &acc); rc != 0 {
+		return rtxErr(rc)
+	}
+	defer C.rtx_accum_destroy(acc)
+	for offered := 0; offered < c.samplesPerPixel; {
+		count := min(passSamples, c.samplesPerPixel-offered)
+		var ad C.rtx_adapt_stats
+		// the open-tile count is the stop signal, so every pass is waited for
+		if rc := C.rtx_accum_add_adaptive(acc, C.uint32_t(count), C.float(relTol), C.uint32_t(max(minSamples, 0)), nil, 0, nil, &ad); rc != 0 {
+			return rtxErr(rc)
+		}
+		offered = int(C.rtx_accum_samples(acc))
+		if ad.open_tiles == 0 {
+			break
+		}
+		if onPass != nil && !onPass(offered, uint64(ad.open_tiles), uint64(ad.open_pixels)) {
+			break
+		}
+	}
+	text := make([]byte, int(C.rtx_ppm_max_bytes(cam.image_width, cam.image_height)))
+	var n C.uint64_t
+	if rc := C.rtx_accum_ppm(acc, (*C.char)(unsafe.Pointer(&text[0])), C.uint64_t(len(text)), &n); rc != 0 {
+		return rtxErr(rc)
+	}
+	if rc := C.rtx_device_check(0); rc != 0 {
+		return rtxErr(rc)
+	}
+	_, err = writer.Write(text[:int(n)])
+	return err
+}
+
 // Guide is one pixel of the first-hit guide images (rtx_guide, rtx.h "denoised previews"): the mean over a range of
 // samples of the albedo, the normal and the depth at the first hit of the render's own camera ray; Cover is the share
 // of the samples that hit anything, and Depth is 0 where none did.

@@ -567,6 +567,72 @@ int rtx_accum_reset(rtx_accum* accum);
 /* Frees the accumulator's device memory (NULL is a no-op).  Blocking. */
 void rtx_accum_destroy(rtx_accum* accum);
 
+/* ---- adaptive sampling (ABI 10, additive) --------------------------
+ * rtx_accum_add samples every pixel in every pass, so "stop when clean" means "stop when the LAST
+ * pixel is clean".  An ADAPTIVE pass samples only the tiles that still hold a noisy pixel.  It is a
+ * separate, opt-in entry: rtx_render* and rtx_accum_add compute what they computed before.
+ *
+ * State.  An accumulator holds one word per TILE of its S / Q layout: open, or closed at n.  A
+ * tile is tile_width x tile_height pixels of the shard (rtx_accum_tile_shape; 64 pixels), tiles
+ * start at the region's x0 and at shard row 0 (the compacted rows of rtx_region), and the tiles of
+ * the right and bottom edges may be partial.  All tiles are open at create and after
+ * rtx_accum_reset.  rtx_accum_samples stays the FRONTIER n: the samples offered so far.  Pixel p
+ * has received n_p samples: n when its tile is open, else the n at which its tile closed.
+ *
+ * The contract that replaces "equal to the one-shot render at n":  a pixel with n_p samples is, bit
+ * for bit, that pixel of a one-shot render of the same region at samples_per_pixel = n_p.
+ *
+ * rtx_accum_add_adaptive does three things in order, all enqueued on hip_stream, with no host
+ * round trip in between:
+ *  1. SELECT.  If n >= max(min_samples, 1): every open tile NONE of whose pixels is NOISY is closed
+ *     at n.  NOISY is rtx_accum_resolve_device's test at (n, rel_tol), the same float32 operations.
+ *     A NaN pixel is not noisy (its comparison is false) and keeps no tile open.  A closed tile
+ *     never reopens before a reset.
+ *  2. SAMPLE.  The samples k = n .. n + count - 1 of every pixel of every tile still open are
+ *     rendered and folded into S and Q exactly as rtx_accum_add does.  A closed tile's S and Q are
+ *     not touched.
+ *  3. n += count, whether or not a tile was open: the host does not know, and does not wait to
+ *     find out.
+ * count == 0, n + count past 2^32 - 1, !(rel_tol >= 0) (a NaN, a negative tolerance) and a NULL
+ * accumulator return RTX_ERR_INVALID_ARG before any device is touched.  So does rtx_accum_add on an
+ * accumulator that has taken an adaptive pass, until it is reset: its tiles no longer share one n.
+ *
+ * A non-NULL stats or adapt_stats synchronises the stream.  adapt_stats: the accumulator's tiles,
+ * the tiles this pass sampled and the pixels in them.  open_tiles == 0 is the caller's stop signal
+ * (such a pass renders nothing, and completes).  stats as rtx_accum_add's, for the samples this
+ * pass rendered: samples = open_pixels * count, kernel_ms (the selection not included), and with
+ * RTX_FLAG_COUNTERS the work counters of exactly those samples.
+ *
+ * Everything that reads an accumulator uses n_p: rtx_accum_resolve* computes inv = 1.0f /
+ * (float)n_p per pixel and counts the noisy pixels at each pixel's own n_p; rtx_accum_ppm and
+ * rtx_accum_preview* resolve likewise (the preview's guides stay over [0, min(n, guide_samples)):
+ * they do not depend on the accumulator's contents).  An accumulator that never took an adaptive
+ * pass runs the kernels and launches it ran before.
+ *
+ * BIAS.  Stopping on an ESTIMATE of the noise biases the result: a tile that has not yet seen its
+ * first firefly (a rare bright sample) looks clean, closes early and stays too dark; min_samples is
+ * the guard.  Neighbouring tiles that stop at different n differ in noise level, so tile edges can
+ * show at loose tolerances.  Not provided: per-pixel granularity, dilation of the open tiles,
+ * reopening, and a gather of accumulators across GPUs (each rank's shard selects on its own).   */
+typedef struct rtx_adapt_stats {
+    uint64_t tiles;       /* tiles of the accumulator's shard */
+    uint64_t open_tiles;  /* tiles this pass sampled */
+    uint64_t open_pixels; /* the pixels of the shard in them */
+} rtx_adapt_stats;
+
+int rtx_accum_add_adaptive(rtx_accum* accum, uint32_t count, float rel_tol, uint32_t min_samples, void* hip_stream,
+                           uint32_t flags, rtx_stats* stats, rtx_adapt_stats* adapt_stats);
+
+/* The accumulator's tile: tile_width x tile_height pixels (a reference can reproduce the selection). */
+int rtx_accum_tile_shape(const rtx_accum* accum, uint32_t* tile_width, uint32_t* tile_height);
+
+/* n_p of every pixel of the region's compacted shard rows, row-major, one uint32 each: a heat map
+ * of where the samples went.  Into device memory on hip_stream (enqueued), or into host memory
+ * after every render enqueued on the device so far (blocking).  Before any adaptive pass every
+ * value is n. */
+int rtx_accum_sample_counts_device(rtx_accum* accum, uint32_t* d_counts, void* hip_stream);
+int rtx_accum_sample_counts(rtx_accum* accum, uint32_t* out_counts);
+
 /* ---- ray queries (ABI 10, additive) ------------------------------
  * The question under Render, the reference's own public interface:
  *   Hittable.Hit(r *Ray, rayT Interval) (HitInfo, bool)          hittables.go:7-20, bvh.go:220-249

@@ -25,9 +25,20 @@ struct rtx_accum {
     // previews, made by the first one: the resolved image, its variance, the guides and the filter's
     // workspace, 12 + 12 + 32 + 32 B per pixel of the shard
     rtxd::DeviceBuffer preview;
-    uint32_t n = 0;
+    // adaptive passes: the open-tile count (u32, padded to 8 B) and the open-pixel count (u64) of the
+    // last selection, then one word per tile (0: open, else the n it closed at), then the list of open tiles
+    rtxd::DeviceBuffer adapt;
+    bool adaptive = false;  // an adaptive pass since create / reset: the tiles no longer share one n
+    uint32_t n = 0;         // the frontier: the samples offered so far
     float* s() const { return sums.as<float>(); }
     float* q() const { return s() + slots * 3; }
+    uint32_t tiles() const { return (uint32_t)(slots / 64); }
+    uint32_t* n_open() const { return adapt.as<uint32_t>(); }
+    unsigned long long* open_pixels() const { return adapt.as<unsigned long long>() + 1; }
+    uint32_t* tile_n() const { return adapt.as<uint32_t>() + 4; }
+    uint32_t* tile_list() const { return tile_n() + tiles(); }
+    size_t adapt_bytes() const { return 16 + 2 * sizeof(uint32_t) * (size_t)tiles(); }
+    const uint32_t* closed_at() const { return adaptive ? tile_n() : nullptr; }  // what a reader of S and Q divides by
 };
 
 namespace {
@@ -45,7 +56,7 @@ size_t accum_bytes(const rtx_accum* a) { return (size_t)a->slots * 3 * sizeof(fl
 int accum_resolve_locked(rtx_accum* a, float* d_rgb, float* d_var, float rel_tol, hipStream_t st, uint64_t* noisy) {
     if (noisy) HIP_TRY(hipMemsetAsync(a->noisy.ptr, 0, sizeof(unsigned long long), st));
     const rtxd::ResolveArgs ra{a->s(), a->q(), d_rgb, d_var, noisy ? a->noisy.as<unsigned long long>() : nullptr,
-                               a->region.width, a->rows, a->tile_w_log2, a->n, rel_tol};
+                               a->region.width, a->rows, a->tile_w_log2, a->n, rel_tol, a->closed_at()};
     HIP_TRY(rtxd::launch_resolve(ra, st));
     if (noisy) {
         unsigned long long h = 0;
@@ -113,8 +124,12 @@ int rtx_accum_create(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const r
     hipError_t e = a->sums.reserve(std::max<size_t>(2 * accum_bytes(a), sizeof(float)));
     if (e == hipSuccess) e = hipMemset(a->sums.ptr, 0, a->sums.bytes);
     if (e == hipSuccess) e = a->noisy.reserve(sizeof(unsigned long long));
+    if (e == hipSuccess) e = a->adapt.reserve(a->adapt_bytes());
+    if (e == hipSuccess) e = hipMemset(a->adapt.ptr, 0, a->adapt.bytes);  // every tile open
     if (e != hipSuccess) {
         a->sums.release();
+        a->noisy.release();
+        a->adapt.release();
         delete a;
         return fail(e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP, "the accumulator's buffers: %s", hipGetErrorString(e));
     }
@@ -127,6 +142,8 @@ int rtx_accum_add(rtx_accum* a, uint32_t count, void* hip_stream, uint32_t flags
     if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
     if (count == 0) return fail(RTX_ERR_INVALID_ARG, "a pass of 0 samples");
     if (a->n + count < a->n) return fail(RTX_ERR_INVALID_ARG, "%u + %u samples exceed 2^32 - 1", a->n, count);
+    if (a->adaptive)
+        return fail(RTX_ERR_INVALID_ARG, "a uniform pass after an adaptive one: the tiles no longer share one n (reset first)");
     if (int rc = accum_device(a)) return rc;
     rtx_scene* s = a->scene;
     std::lock_guard<std::mutex> lk(s->mu);
@@ -145,7 +162,99 @@ int rtx_accum_add(rtx_accum* a, uint32_t count, void* hip_stream, uint32_t flags
     return rc;
 }
 
+int rtx_accum_add_adaptive(rtx_accum* a, uint32_t count, float rel_tol, uint32_t min_samples, void* hip_stream,
+                           uint32_t flags, rtx_stats* stats, rtx_adapt_stats* adapt_stats) {
+    g_last_error.clear();
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    if (count == 0) return fail(RTX_ERR_INVALID_ARG, "a pass of 0 samples");
+    if (a->n + count < a->n) return fail(RTX_ERR_INVALID_ARG, "%u + %u samples exceed 2^32 - 1", a->n, count);
+    if (!(rel_tol >= 0.0f)) return fail(RTX_ERR_INVALID_ARG, "rel_tol %g: a tolerance is >= 0", (double)rel_tol);
+    if (int rc = accum_device(a)) return rc;
+    rtx_scene* s = a->scene;
+    hipStream_t st = (hipStream_t)hip_stream;
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceCopy* c = nullptr;
+    if (int rc = ensure_device(s, a->device, &c)) return rc;
+    const bool live = a->slots != 0;  // (an empty shard: no tile, nothing to select or render)
+    if (live) {
+        // select: on the pass's stream, after every render on the device (the last pass may have run on another stream)
+        if (int rc = wait_for_renders(a->device, st)) return rc;
+        HIP_TRY(hipMemsetAsync(a->adapt.ptr, 0, 16, st));
+        const rtxd::SelectArgs sel{a->s(), a->q(), a->tile_n(), a->tile_list(), a->n_open(), a->open_pixels(),
+                                   a->region.width, a->rows, a->tile_w_log2, a->n, rel_tol,
+                                   a->n >= std::max(min_samples, 1u) ? 1u : 0u};
+        HIP_TRY(rtxd::launch_select(sel, st));
+        a->adaptive = true;  // (from here on: the selection may have closed tiles even if the pass fails below)
+    }
+    // sample: the pass's launches read the list and its count from device memory
+    const rtxd::SampleRange pass{a->n, count, a->s(), a->q(), live ? a->tile_list() : nullptr, live ? a->n_open() : nullptr};
+    uint32_t chunks = 0;
+    bool tiered = false;
+    if (int rc = enqueue_on(s, c, &a->cam, a->seed, &a->region, nullptr, st, flags, stats != nullptr, &chunks, &tiered, &pass,
+                            a->slots))
+        return rc;
+    a->n += count;
+    a->adaptive = true;
+    if (!stats && !adapt_stats) return RTX_OK;
+    struct {
+        uint32_t n_open, pad;
+        unsigned long long open_pixels;
+    } h = {0u, 0u, 0ull};
+    HIP_TRY(hipStreamSynchronize(st));
+    if (live) HIP_TRY(hipMemcpy(&h, a->adapt.ptr, sizeof(h), hipMemcpyDeviceToHost));
+    if (adapt_stats) {
+        adapt_stats->tiles = a->tiles();
+        adapt_stats->open_tiles = h.n_open;
+        adapt_stats->open_pixels = h.open_pixels;
+    }
+    if (!stats) return RTX_OK;
+    const int rc = collect_on(c, (flags & RTX_FLAG_COUNTERS) != 0, (uint64_t)h.open_pixels * count, chunks, stats);
+    stats->walk_layout = walk_layout(s, &a->cam, tiered);
+    return rc;
+}
+
 uint32_t rtx_accum_samples(const rtx_accum* a) { return a ? a->n : 0u; }
+
+int rtx_accum_tile_shape(const rtx_accum* a, uint32_t* tile_width, uint32_t* tile_height) {
+    g_last_error.clear();
+    if (!a || !tile_width || !tile_height) return fail(RTX_ERR_INVALID_ARG, "NULL argument");
+    *tile_width = 1u << a->tile_w_log2;
+    *tile_height = 64u >> a->tile_w_log2;
+    return RTX_OK;
+}
+
+int rtx_accum_sample_counts_device(rtx_accum* a, uint32_t* d_counts, void* hip_stream) {
+    g_last_error.clear();
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    if (!d_counts && (uint64_t)a->rows * a->region.width) return fail(RTX_ERR_INVALID_ARG, "NULL output");
+    if (int rc = accum_device(a)) return rc;
+    std::lock_guard<std::mutex> lk(a->scene->mu);
+    HIP_TRY(rtxd::launch_counts(a->closed_at(), d_counts, a->region.width, a->rows, a->tile_w_log2, a->n,
+                                (hipStream_t)hip_stream));
+    return RTX_OK;
+}
+
+int rtx_accum_sample_counts(rtx_accum* a, uint32_t* out_counts) {
+    g_last_error.clear();
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    const size_t bytes = (size_t)a->rows * a->region.width * sizeof(uint32_t);
+    if (!out_counts && bytes) return fail(RTX_ERR_INVALID_ARG, "NULL output");
+    if (int rc = accum_device(a)) return rc;
+    std::lock_guard<std::mutex> lk(a->scene->mu);
+    std::lock_guard<std::mutex> bl(g_render_mu);  // the cached buffer and stream
+    hipStream_t st = render_stream(a->device);
+    uint32_t* cnt = static_cast<uint32_t*>(render_buffer(a->device, -6, std::max<size_t>(1, bytes)));
+    if (!st) return fail(RTX_ERR_HIP, "stream on device %d", a->device);
+    if (!cnt) return fail(RTX_ERR_OOM, "device buffer for a %ux%u count map", a->region.width, a->rows);
+    if (int rc = wait_for_renders(a->device, st)) return rc;  // the selections ran on the passes' streams, before them
+    int rc = RTX_OK;
+    if (rtxd::launch_counts(a->closed_at(), cnt, a->region.width, a->rows, a->tile_w_log2, a->n, st) != hipSuccess)
+        rc = fail(RTX_ERR_HIP, "the count map's launch");
+    if (rc == RTX_OK && bytes && copy_to_host(out_counts, cnt, bytes, st) != hipSuccess)
+        rc = fail(RTX_ERR_HIP, "copying the count map to the host");
+    (void)hipStreamSynchronize(st);
+    return rc;
+}
 
 int rtx_accum_resolve_device(rtx_accum* a, float* d_rgb, float* d_var, float rel_tol, void* hip_stream, uint64_t* noisy) {
     g_last_error.clear();
@@ -262,6 +371,8 @@ int rtx_accum_reset(rtx_accum* a) {
     std::lock_guard<std::mutex> lk(a->scene->mu);
     HIP_TRY(hipDeviceSynchronize());  // passes and resolves in flight, on any stream
     HIP_TRY(hipMemset(a->sums.ptr, 0, a->sums.bytes));
+    HIP_TRY(hipMemset(a->adapt.ptr, 0, a->adapt.bytes));  // every tile open again
+    a->adaptive = false;
     a->n = 0;
     return RTX_OK;
 }
@@ -275,6 +386,7 @@ void rtx_accum_destroy(rtx_accum* a) {
             a->sums.release();
             a->noisy.release();
             a->preview.release();
+            a->adapt.release();
         }
     }
     delete a;

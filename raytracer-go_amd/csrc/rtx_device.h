@@ -523,6 +523,12 @@ struct Params {
     // waits on, in every phase that defers)
     uint32_t drain_lds;
     uint32_t drain;          // 1: the timed tiered render drains (RTX_DRAIN=0: the far pass's own launch, A/B)
+    // (last again: every field above keeps its kernel-argument offset) an adaptive pass of an accumulator
+    // (rtx_accum_add_adaptive): the tiles still open, listed by select_tiles in no particular order, and
+    // their count, in device memory.  The TIER 0 / 1 unit claim hands out the units of the listed tiles only and
+    // accumulate_listed folds only them; nullptr (every other render): all tiles, as before.
+    const uint32_t* tile_list;
+    const uint32_t* n_open;
 };
 constexpr uint32_t DRAIN_WORDS = 16384;  // Params::drain_count's words: near grids up to 8192 workgroups
 

@@ -197,7 +197,8 @@ const RcclApi* rccl_api();  // g_rccl_mu held
 // rtx_render's per-device buffers (bands, the gathered bands, the assembled image), stream and
 // gather events, kept between calls and freed by rtx_release_device_memory; g_render_mu is held
 // for a whole rtx_render.  Keyed by (device, slot): slot d >= 0 is band d, -1 the gather, -2 the
-// image, -3 / -4 the image and text of rtx_render_ppm and rtx_accum_ppm, -5 rtx_accum_resolve's variance.
+// image, -3 / -4 the image and text of rtx_render_ppm and rtx_accum_ppm, -5 rtx_accum_resolve's variance,
+// -6 rtx_accum_sample_counts' map.
 // Each wants the current device = device and g_render_mu held, and returns nullptr on failure.
 extern std::mutex g_render_mu;
 void* render_buffer(int device, int slot, size_t bytes);

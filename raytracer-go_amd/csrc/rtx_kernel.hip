@@ -256,10 +256,16 @@ __device__ __forceinline__ void split_clk(uint64_t& acc, uint64_t& clk) {
 // DRAIN (render_drain): TIER 1 writes the records to the workgroup's own region of the queue
 // (Params::drain_region, counted in LDS at drain_lds); TIER 2 resumes that region's records only, its units claimed
 // by the workgroup's waves.
+//
+// ADAPT (an adaptive pass of an accumulator; TIER 0 / 1): the units are those of the open tiles listed in
+// Params::tile_list, *Params::n_open of them; the unit's tile is the list's entry.  Nothing else differs: the scratch,
+// S and Q are addressed by the real tile.  A template flag, not a runtime test of the pointer: the test alone moved the
+// register allocation of the kernels that never take it (§36).
 template <bool COUNT, bool USE_LDS, bool QUADS, bool NOISE, int WAVES, bool HYB, bool CLK, int TIER, bool POOL, bool ST,
-          bool DRAIN>
+          bool DRAIN, bool ADAPT = false>
 __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 = 0) {
     constexpr bool TIME = COUNT || CLK;
+    static_assert(!ADAPT || TIER <= 1, "the open-tile list: the passes that claim units of tiles from the global counter");
     static_assert(!DRAIN || (!COUNT && !CLK && (TIER == 1 || TIER == 2)), "the drain: the timed near and far passes");
     static_assert(!POOL || (USE_LDS && (TIER == 0 || TIER == 1)), "the camera-ray pool: LDS scenes, near pass or one walk");
     if constexpr (TIER == 3) {
@@ -326,8 +332,12 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
     // redo pass: the compacted list of flagged samples when it held them all (else the bits, unit by unit)
     const uint32_t n_ids = TIER == 3 ? __builtin_amdgcn_readfirstlane(*(volatile uint32_t*)p.redo_count) : 0u;
     const bool listed = TIER == 3 && n_ids <= p.redo_cap;
+    // ADAPT: the units of the open tiles only, their count read from device memory as n_rec is (the redo pass scans the
+    // bits of every tile: closed ones have none set)
+    uint32_t n_claim = n_tiles;
+    if constexpr (ADAPT) n_claim = min(__builtin_amdgcn_readfirstlane(*(volatile const uint32_t*)p.n_open), n_tiles);
     const uint64_t n_units = TIER == 2 ? (uint64_t)((n_rec + 63u) / 64u)
-                                       : (listed ? (uint64_t)((n_ids + 63u) / 64u) : (uint64_t)n_tiles * nsub);
+                                       : (listed ? (uint64_t)((n_ids + 63u) / 64u) : (uint64_t)n_claim * nsub);
     if (TIER == 2 && (DRAIN || blockIdx.x == 0) && threadIdx.x == 0 && n_rec)
         atomicAdd(&p.counters[CNT_DEFERRED_PATHS], (unsigned long long)n_rec);  // deferred paths, all chunks
     const size_t tile_floats = (size_t)n_tiles * 64 * 3;  // one sample of every tile (tile-major scratch)
@@ -553,10 +563,18 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
                     cursor = 0;
                 } else if (!exhausted) {
                     u_tile = uu / nsub;
+                    if constexpr (ADAPT) {
+                        // The unit's tile is the list's entry (its samples: by its place in the list).  The list's
+                        // address is read from the kernel arguments here (uniform: scalar loads), so the walk keeps
+                        // no register for it (§24's pattern).
+                        u_k0 = p.k0 + (uu - u_tile * nsub) * p.sub;
+                        const uint32_t* const open = (RTX_KARG_RELOAD ? karg_params() : p).tile_list;
+                        u_tile = min(__builtin_amdgcn_readfirstlane(open[u_tile]), n_tiles - 1u);  // (a listed tile: in range)
+                    }
                     u_x = (u_tile % tiles_x) << twl;
                     u_r = (u_tile / tiles_x) * th;
                     if constexpr (ST) u_y = p.y0 + region_row(u_r, p.rank, p.world, p.stripe_log2);
-                    u_k0 = p.k0 + (uu - u_tile * nsub) * p.sub;
+                    if constexpr (!ADAPT) u_k0 = p.k0 + (uu - u_tile * nsub) * p.sub;
                     const uint32_t cnt_k = min(p.sub, p.k0 + p.kn - u_k0);
                     u_items = 64u * cnt_k;
                     cursor = 0;
@@ -723,9 +741,9 @@ __device__ __forceinline__ void render_body(const Params& p, const uint64_t t0 =
 }
 
 template <bool COUNT, bool USE_LDS, bool QUADS, bool NOISE, int WAVES = 8, int MINW = 0, bool HYB = false,
-          bool CLK = false, int TIER = 0, bool POOL = false, bool ST = false>
+          bool CLK = false, int TIER = 0, bool POOL = false, bool ST = false, bool ADAPT = false>
 __global__ __launch_bounds__(64 * WAVES, MINW) void render_items(Params p) {
-    render_body<COUNT, USE_LDS, QUADS, NOISE, WAVES, HYB, CLK, TIER, POOL, ST, false>(p);
+    render_body<COUNT, USE_LDS, QUADS, NOISE, WAVES, HYB, CLK, TIER, POOL, ST, false, ADAPT>(p);
 }
 
 // The timed tiered render's near pass with its drain: the near phase (pn, the near tree, records to the
@@ -746,7 +764,7 @@ struct DrainArgs {
     FarLayout fl;
 };
 
-template <bool USE_LDS, int WAVES, int MINW, bool HYB, bool POOL, bool ST, bool QUADS = false>
+template <bool USE_LDS, int WAVES, int MINW, bool HYB, bool POOL, bool ST, bool QUADS = false, bool ADAPT = false>
 __global__ __launch_bounds__(64 * WAVES, MINW) void render_drain(DrainArgs a) {
     const uint64_t t0 = __builtin_amdgcn_s_memrealtime() | 1ull;  // the watchdog's start for both phases (nonzero)
     {  // the workgroup's two drain words in LDS (past both phases' layouts): zero first
@@ -754,7 +772,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void render_drain(DrainArgs a) {
         if (threadIdx.x < 2) reinterpret_cast<uint32_t*>(lds_words + a.pn.drain_lds)[threadIdx.x] = 0u;
         __syncthreads();
     }
-    render_body<false, USE_LDS, QUADS, false, WAVES, HYB, false, 1, POOL, ST, true>(a.pn, t0);
+    render_body<false, USE_LDS, QUADS, false, WAVES, HYB, false, 1, POOL, ST, true, ADAPT>(a.pn, t0);
     __syncthreads();  // every wave's near work and records done: the far phase overwrites the scene copy
     // The far phase reads its settings from the kernel arguments afresh, through an opaque copy of their address:
     // values it shares with the near phase are then not kept live through the near phase (which spilled 4 more VGPRs).
@@ -876,17 +894,11 @@ __global__ __launch_bounds__(256) void reduce_samples(Params p, uint32_t last) {
 // zero), so a wave reads and writes 768 contiguous bytes of each, once per chunk.  Always a continuation: the buffers
 // are zero at create and after reset.  c * c is rounded to float32 before the add (__fmul_rn: never contracted).
 // It clears the chunk's redo bits as reduce_samples does.
-__global__ __launch_bounds__(256) void accumulate_samples(Params p, float* acc_s, float* acc_q) {
+// (the body of accumulate_samples and of its sibling over the open tiles of an adaptive pass, accumulate_listed: slot i
+// of the n_tiles tiles)
+__device__ __forceinline__ void accumulate_slot(const Params& p, float* acc_s, float* acc_q, const size_t i,
+                                                const uint32_t tiles_x, const size_t n_tiles) {
     const uint32_t twl = p.tile_w_log2;
-    const uint32_t tiles_x = tiles_x_of(p.width, twl);
-    const size_t n_tiles = (size_t)tiles_x * tiles_y_of(p.rows, twl);
-    if (p.redo_count && __builtin_amdgcn_readfirstlane(*(volatile uint32_t*)p.redo_count) > p.redo_cap) {
-        const uint64_t words = (uint64_t)p.kn * n_tiles * 2;  // 64 bits a tile
-        for (uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x; w < words; w += (uint64_t)gridDim.x * 256)
-            p.redo_bits[w] = 0u;
-    }
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_tiles * 64) return;
     const uint32_t t = (uint32_t)(i >> 6), l = (uint32_t)(i & 63u);
     const uint32_t lx = ((t % tiles_x) << twl) + (l & ((1u << twl) - 1u)), lr = (t / tiles_x) * (64u >> twl) + (l >> twl);
     if (lx >= p.width || lr >= p.rows) return;  // outside a ragged tile: its S and Q stay zero
@@ -932,6 +944,57 @@ __global__ __launch_bounds__(256) void accumulate_samples(Params p, float* acc_s
     q[2] = qz;
 }
 
+// The chunk's redo bits back to zero when the redo list overflowed (reduce_samples).
+__device__ __forceinline__ void clear_redo_bits(const Params& p, const size_t n_tiles) {
+    if (p.redo_count && __builtin_amdgcn_readfirstlane(*(volatile uint32_t*)p.redo_count) > p.redo_cap) {
+        const uint64_t words = (uint64_t)p.kn * n_tiles * 2;  // 64 bits a tile
+        for (uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x; w < words; w += (uint64_t)gridDim.x * 256)
+            p.redo_bits[w] = 0u;
+    }
+}
+
+__global__ __launch_bounds__(256) void accumulate_samples(Params p, float* acc_s, float* acc_q) {
+    const uint32_t tiles_x = tiles_x_of(p.width, p.tile_w_log2);
+    const size_t n_tiles = (size_t)tiles_x * tiles_y_of(p.rows, p.tile_w_log2);
+    clear_redo_bits(p, n_tiles);
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_tiles * 64) return;
+    accumulate_slot(p, acc_s, acc_q, i, tiles_x, n_tiles);
+}
+
+// accumulate_samples for an adaptive pass: wave w folds the tile p.tile_list[w] when w < *p.n_open,
+// and no other.  The scratch slots of a closed tile hold colours of earlier renders: they are never read, and a closed
+// tile's S and Q are never written.  The launch covers every tile (the host does not know how many are open).
+__global__ __launch_bounds__(256) void accumulate_listed(Params p, float* acc_s, float* acc_q) {
+    const uint32_t tiles_x = tiles_x_of(p.width, p.tile_w_log2);
+    const size_t n_tiles = (size_t)tiles_x * tiles_y_of(p.rows, p.tile_w_log2);
+    clear_redo_bits(p, n_tiles);
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t n_open = min((size_t)*p.n_open, n_tiles);
+    if ((i >> 6) >= n_open) return;
+    const size_t t = p.tile_list[i >> 6];
+    if (t >= n_tiles) return;  // (never: select_tiles lists tiles of this layout)
+    accumulate_slot(p, acc_s, acc_q, t * 64 + (i & 63u), tiles_x, n_tiles);
+}
+
+// One pixel of rtx_accum_resolve_device from its S and Q after n samples: the mean m, the variance of the mean v, and
+// whether it is NOISY at rel_tol, in float32 exactly as rtx.h states (no square root, no contraction).  resolve_accum
+// and select_tiles share it: an adaptive pass closes a tile by the test a resolve would count it with.
+__device__ __forceinline__ bool resolve_pixel(const float* s, const float* q, const uint32_t n, const float rel_tol,
+                                              float m[3], float v[3]) {
+    const float inv = 1.0f / (float)n;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        m[c] = __fmul_rn(s[c], inv);
+        const float d = __fsub_rn(__fmul_rn(q[c], inv), __fmul_rn(m[c], m[c]));
+        v[c] = __fmul_rn(d > 0.0f ? d : 0.0f, inv);  // (a NaN compares false: 0)
+    }
+    const float sv = __fadd_rn(__fadd_rn(v[0], v[1]), v[2]);
+    const float mb = __fadd_rn(__fadd_rn(m[0], m[1]), m[2]);
+    const float tol = __fmul_rn(rel_tol, mb > 0.01f ? mb : 0.01f);
+    return sv > __fmul_rn(tol, tol);
+}
+
 // rtx_accum_resolve_device: the mean, the biased variance of the mean and the noisy-pixel count of an accumulator
 // after n samples, in float32 exactly as rtx.h states (no square root, no contraction).  Thread i reads slot i of the
 // tile-major S and Q and writes its pixel's row of the row-major outputs.  Every thread of a wave reaches the ballot —
@@ -947,16 +1010,11 @@ __global__ __launch_bounds__(256) void resolve_accum(ResolveArgs a) {
     const bool live = i < n_tiles * 64 && lx < a.width && lr < a.rows;
     bool noisy = false;
     if (live) {
-        const float* s = a.s + i * 3;
-        const float* q = a.q + i * 3;
-        const float inv = 1.0f / (float)a.n;
+        // an accumulator with adaptive passes (a.tile_n): a closed tile's pixels stopped at its word
+        uint32_t n = a.n;
+        if (a.tile_n && a.tile_n[t]) n = a.tile_n[t];
         float m[3], v[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            m[c] = __fmul_rn(s[c], inv);
-            const float d = __fsub_rn(__fmul_rn(q[c], inv), __fmul_rn(m[c], m[c]));
-            v[c] = __fmul_rn(d > 0.0f ? d : 0.0f, inv);  // (a NaN compares false: 0)
-        }
+        noisy = resolve_pixel(a.s + i * 3, a.q + i * 3, n, a.rel_tol, m, v);
         const size_t o = ((size_t)lr * a.width + lx) * 3;
         a.rgb[o] = m[0];
         a.rgb[o + 1] = m[1];
@@ -966,10 +1024,6 @@ __global__ __launch_bounds__(256) void resolve_accum(ResolveArgs a) {
             a.var[o + 1] = v[1];
             a.var[o + 2] = v[2];
         }
-        const float sv = __fadd_rn(__fadd_rn(v[0], v[1]), v[2]);
-        const float mb = __fadd_rn(__fadd_rn(m[0], m[1]), m[2]);
-        const float tol = __fmul_rn(a.rel_tol, mb > 0.01f ? mb : 0.01f);
-        noisy = sv > __fmul_rn(tol, tol);
     }
     if (a.noisy) {  // (uniform: a kernel argument)
         const unsigned long long votes = __ballot(noisy);
@@ -984,11 +1038,95 @@ hipError_t launch_resolve(const ResolveArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// The selection of an adaptive pass (rtx_accum_add_adaptive), a wave per tile (lane l on slot 64 t + l,
+// as in resolve_accum).  An open tile (word 0) none of whose live pixels is NOISY by resolve_pixel at (n, rel_tol) is closed at n
+// when a.close says the pass may close (n >= max(min_samples, 1), so a closed tile's word is never 0); every tile
+// still open is appended to tile_list, counted in *n_open, its live pixels in *open_pixels (both zeroed by the caller).
+// Every lane reaches the ballots and the barriers: a padded or ragged slot, and a wave past the last tile, vote "not
+// noisy"; nothing returns early.  A workgroup of 16 waves takes 64 consecutive tiles, four per wave, collects its open
+// tiles in LDS and appends them with ONE atomic on *n_open (one atomic per tile, 32400 on one address for a 1920 x 1080
+// shard, took 0.76 ms: forty times the kernel's memory traffic).
+constexpr uint32_t SELECT_WAVES = 16, SELECT_PER_WAVE = 4, SELECT_TILES = SELECT_WAVES * SELECT_PER_WAVE;
+__global__ __launch_bounds__(64 * SELECT_WAVES) void select_tiles(SelectArgs a) {
+    __shared__ uint32_t s_list[SELECT_TILES];
+    __shared__ uint32_t s_n, s_pixels, s_base;
+    if (threadIdx.x == 0) s_n = s_pixels = 0u;
+    __syncthreads();
+    const uint32_t twl = a.tile_w_log2;
+    const uint32_t tiles_x = tiles_x_of(a.width, twl);
+    const size_t n_tiles = (size_t)tiles_x * tiles_y_of(a.rows, twl);
+    const uint32_t l = threadIdx.x & 63u;
+    for (uint32_t j = 0; j < SELECT_PER_WAVE; ++j) {
+        const size_t tt = ((size_t)blockIdx.x * SELECT_WAVES + (threadIdx.x >> 6)) * SELECT_PER_WAVE + j;
+        const bool tile = tt < n_tiles;  // (uniform: a wave is on one tile)
+        const uint32_t t = tile ? (uint32_t)tt : 0u;
+        const uint32_t lx = ((t % tiles_x) << twl) + (l & ((1u << twl) - 1u)), lr = (t / tiles_x) * (64u >> twl) + (l >> twl);
+        const bool live = tile && lx < a.width && lr < a.rows;
+        const uint32_t word = tile ? a.tile_n[t] : 1u;
+        bool noisy = false;
+        if (live && a.close && word == 0u) {
+            float m[3], v[3];
+            const size_t i = (size_t)t * 64 + l;
+            noisy = resolve_pixel(a.s + i * 3, a.q + i * 3, a.n, a.rel_tol, m, v);
+        }
+        const unsigned long long votes = __ballot(noisy), lives = __ballot(live);
+        if (tile && word == 0u && l == 0u) {  // (closed before: it never reopens)
+            if (a.close && votes == 0ull) {
+                a.tile_n[t] = a.n;
+            } else {
+                s_list[atomicAdd(&s_n, 1u)] = t;  // (at most SELECT_TILES appends: one per tile of the workgroup)
+                atomicAdd(&s_pixels, (uint32_t)__popcll(lives));
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_n) {
+        s_base = atomicAdd(a.n_open, s_n);  // (the sum over all workgroups is at most n_tiles)
+        atomicAdd(a.open_pixels, (unsigned long long)s_pixels);
+    }
+    __syncthreads();
+    if (threadIdx.x < s_n) a.tile_list[s_base + threadIdx.x] = s_list[threadIdx.x];
+}
+
+hipError_t launch_select(const SelectArgs& a, hipStream_t stream) {
+    if (a.width == 0 || a.rows == 0) return hipSuccess;
+    const uint64_t tiles = (uint64_t)tiles_x_of(a.width, a.tile_w_log2) * tiles_y_of(a.rows, a.tile_w_log2);
+    hipLaunchKernelGGL(select_tiles, dim3((uint32_t)((tiles + SELECT_TILES - 1) / SELECT_TILES)), dim3(64 * SELECT_WAVES), 0,
+                       stream, a);
+    return hipGetLastError();
+}
+
+// rtx_accum_sample_counts_device: n_p of every pixel, row-major: its tile's word when the tile is closed, else the
+// frontier n (tile_n == nullptr: an accumulator without adaptive passes, every tile open).
+__global__ __launch_bounds__(256) void tile_counts(const uint32_t* tile_n, uint32_t* out, uint32_t width, uint32_t rows,
+                                                   uint32_t twl, uint32_t n) {
+    const uint32_t tiles_x = tiles_x_of(width, twl);
+    const size_t n_tiles = (size_t)tiles_x * tiles_y_of(rows, twl);
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_tiles * 64) return;
+    const uint32_t t = (uint32_t)(i >> 6), l = (uint32_t)(i & 63u);
+    const uint32_t lx = ((t % tiles_x) << twl) + (l & ((1u << twl) - 1u)), lr = (t / tiles_x) * (64u >> twl) + (l >> twl);
+    if (lx >= width || lr >= rows) return;
+    const uint32_t word = tile_n ? tile_n[t] : 0u;
+    out[(size_t)lr * width + lx] = word ? word : n;
+}
+
+hipError_t launch_counts(const uint32_t* tile_n, uint32_t* out, uint32_t width, uint32_t rows, uint32_t tile_w_log2,
+                         uint32_t n, hipStream_t stream) {
+    if (width == 0 || rows == 0) return hipSuccess;
+    const uint64_t slots = (uint64_t)tiles_x_of(width, tile_w_log2) * tiles_y_of(rows, tile_w_log2) * 64;
+    hipLaunchKernelGGL(tile_counts, dim3((uint32_t)((slots + 255) / 256)), dim3(256), 0, stream, tile_n, out, width, rows,
+                       tile_w_log2, n);
+    return hipGetLastError();
+}
+
 // The chunk's reduction: reduce_samples into p.out (a one-shot render; `last` scales by 1/spp), or
 // accumulate_samples into an accumulator's S and Q.
 inline void launch_reduce(const Params& p, const SampleRange& rg, uint64_t slots, bool last, hipStream_t stream) {
     const dim3 grid((uint32_t)((slots + 255) / 256));
-    if (rg.s)
+    if (rg.s && p.tile_list)  // an adaptive pass: the open tiles only
+        hipLaunchKernelGGL(accumulate_listed, grid, dim3(256), 0, stream, p, rg.s, rg.q);
+    else if (rg.s)
         hipLaunchKernelGGL(accumulate_samples, grid, dim3(256), 0, stream, p, rg.s, rg.q);
     else
         hipLaunchKernelGGL(reduce_samples, grid, dim3(256), 0, stream, p, (uint32_t)last);
@@ -1036,10 +1174,13 @@ hipError_t launch_items(Params p, bool use_lds, hipStream_t stream, const Sample
     const size_t shmem = POOL ? (size_t)pool_f4_offset(p) * 16 + WAVES * POOL_BYTES_PER_WAVE
                               : use_lds ? lds_fixed_bytes(p.n_entries, p.n_quads, p.n_materials, p.n_textures)
                                         : (hyb ? lds_hot_bytes(p.n_hot) : 0);
-    const auto kern = POOL      ? render_items<COUNT, true, QUADS, NOISE, WAVES, MINW, false, CLK, 0, POOL, ST>
-                      : use_lds ? render_items<COUNT, true, QUADS, NOISE, WAVES, MINW, false, CLK, 0, false, ST>
-                                : (hyb ? render_items<COUNT, false, QUADS, NOISE, WAVES, MINW, !NOISE, CLK, 0, false, ST>
-                                       : render_items<COUNT, false, QUADS, NOISE, WAVES, MINW, false, CLK, 0, false, ST>);
+    // (an adaptive pass of an accumulator: the ADAPT instantiation of the same kernel)
+#define RTX_ITEMS(...) (p.tile_list ? render_items<__VA_ARGS__, true> : render_items<__VA_ARGS__, false>)
+    const auto kern = POOL      ? RTX_ITEMS(COUNT, true, QUADS, NOISE, WAVES, MINW, false, CLK, 0, POOL, ST)
+                      : use_lds ? RTX_ITEMS(COUNT, true, QUADS, NOISE, WAVES, MINW, false, CLK, 0, false, ST)
+                                : (hyb ? RTX_ITEMS(COUNT, false, QUADS, NOISE, WAVES, MINW, !NOISE, CLK, 0, false, ST)
+                                       : RTX_ITEMS(COUNT, false, QUADS, NOISE, WAVES, MINW, false, CLK, 0, false, ST));
+#undef RTX_ITEMS
     constexpr int block = 64 * WAVES;
     int cus = 0, per_cu = 0;
     hipError_t e = resident_grid((const void*)kern, block, shmem, &per_cu, &cus);
@@ -1087,7 +1228,9 @@ template <bool COUNT, int WAVES, int MINW, bool CLK = false, bool USE_LDS = true
           bool ST = false, bool QUADS = false, int WN = POOL ? RTX_POOL_WAVES : WAVES>
 hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream, const SampleRange& rg) {
     constexpr int MN = POOL && MINW ? RTX_POOL_MINW : MINW;  // the near (and drain) kernel's waves per SIMD
-    const auto kn = render_items<COUNT, USE_LDS, QUADS, false, WN, MN, HYB, CLK, 1, POOL, ST>;
+    const bool adapt = pn.tile_list != nullptr;  // an adaptive pass: the near pass's (and the drain's) ADAPT instantiation
+    const auto kn = adapt ? render_items<COUNT, USE_LDS, QUADS, false, WN, MN, HYB, CLK, 1, POOL, ST, true>
+                          : render_items<COUNT, USE_LDS, QUADS, false, WN, MN, HYB, CLK, 1, POOL, ST, false>;
     const auto kf = render_items<COUNT, USE_LDS, QUADS, false, WAVES, MINW, HYB, CLK, 2>;  // (rows from the records)
     const auto kr = render_items<COUNT, USE_LDS, QUADS, false, WAVES, MINW, HYB, false, 3, false, ST>;
     const size_t sn = POOL ? (size_t)pool_f4_offset(pn) * 16 + WN * POOL_BYTES_PER_WAVE : items_shmem(pn, USE_LDS, HYB),
@@ -1102,8 +1245,11 @@ hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream, const SampleR
     // same LDS (the larger of the two layouts), when that keeps the near pass's occupancy.
     // (Not for a scene in HBM with LDS caches: the combined kernel spilled 24 VGPRs there, and config 4 took +2.3 %.)
     constexpr bool CAN_DRAIN = !COUNT && !CLK && !HYB;
-    const void* kd = nullptr;
-    if constexpr (CAN_DRAIN) kd = (const void*)render_drain<USE_LDS, WN, MN, HYB, POOL, ST, QUADS>;
+    void (*kdrain)(DrainArgs) = nullptr;
+    if constexpr (CAN_DRAIN)
+        kdrain = adapt ? render_drain<USE_LDS, WN, MN, HYB, POOL, ST, QUADS, true>
+                       : render_drain<USE_LDS, WN, MN, HYB, POOL, ST, QUADS, false>;
+    const void* kd = (const void*)kdrain;
     // (the drain's two per-workgroup words in LDS after the larger layout)
     const size_t sl = ((sn > sf ? sn : sf) + 15) / 16 * 16, sd = sl + 16;
     pn.drain_lds = (uint32_t)(sl / 16);
@@ -1141,8 +1287,7 @@ hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream, const SampleR
         if (drain_now) {
             pn.drain_region = pf.drain_region = pn.defer_cap / (uint32_t)bn;
             if constexpr (CAN_DRAIN)
-                hipLaunchKernelGGL((render_drain<USE_LDS, WN, MN, HYB, POOL, ST, QUADS>), dim3((uint32_t)bn), dim3(block_n), sd,
-                                   stream, DrainArgs{pn, far_layout(pf)});
+                hipLaunchKernelGGL(kdrain, dim3((uint32_t)bn), dim3(block_n), sd, stream, DrainArgs{pn, far_layout(pf)});
         } else {
             hipLaunchKernelGGL(kn, dim3((uint32_t)bn), dim3(block_n), sn, stream, pn);
             hipLaunchKernelGGL(kf, dim3((uint32_t)per_f * cus), dim3(block), sf, stream, pf);

@@ -220,6 +220,10 @@ int enqueue_on(rtx_scene* s, DeviceCopy* c, const rtx_camera* cam, uint64_t seed
     if (int rc = ensure_layout(s, c, cam)) return rc;
     rtxd::Params p = make_params(s, c, oct, cam, seed, r, d_out);
     if (!(p.error_flag = kerr_word(c->device))) return fail(RTX_ERR_OOM, "the error word on device %d", c->device);
+    if (pass) {  // an adaptive pass: its open tiles (a tiered render's passes copy p below)
+        p.tile_list = pass->tile_list;
+        p.n_open = pass->n_open;
+    }
     // the tiered walk: a camera in the near region of a sphere scene (rtx_scene_near_region's rule)
     bool tier = camera_in_near(s, cam) && !p.has_noise;
     rtxd::Params pn;

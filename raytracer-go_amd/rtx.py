@@ -178,6 +178,13 @@ class GuideStats(ctypes.Structure):  # rtx_guide_stats
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class AdaptStats(ctypes.Structure):  # rtx_adapt_stats
+    _fields_ = [("tiles", c_uint64), ("open_tiles", c_uint64), ("open_pixels", c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class DenoiseParams(ctypes.Structure):  # rtx_denoise_params; DenoiseParams.defaults() = rtx_denoise_defaults
     _fields_ = [("iterations", c_uint32), ("sigma_normal", c_float), ("sigma_depth", c_float),
                 ("sigma_luminance", c_float)]
@@ -228,6 +235,8 @@ RTX_SYMBOLS = [
     # denoised previews (ABI 10, additive)
     "rtx_guides_device", "rtx_guides", "rtx_denoise_defaults", "rtx_denoise_workspace_bytes", "rtx_denoise_device",
     "rtx_denoise", "rtx_accum_preview_device", "rtx_accum_preview", "rtx_accum_preview_ppm",
+    # adaptive sampling (ABI 10, additive)
+    "rtx_accum_add_adaptive", "rtx_accum_tile_shape", "rtx_accum_sample_counts_device", "rtx_accum_sample_counts",
 ]
 RTXHOST_SYMBOLS = [
     "rtxhost_build_scene", "rtxhost_scene_free", "rtxhost_scene_desc", "rtxhost_scene_camera",
@@ -380,6 +389,16 @@ def load() -> ctypes.CDLL:
         L.rtx_accum_preview_ppm.argtypes = [c_void_p, c_uint32, POINTER(DenoiseParams), c_void_p, c_uint64,
                                             POINTER(c_uint64)]
         L.rtx_accum_preview_ppm.restype = c_int
+    if hasattr(L, "rtx_accum_add_adaptive"):  # adaptive sampling (ABI 10, additive)
+        L.rtx_accum_add_adaptive.argtypes = [c_void_p, c_uint32, c_float, c_uint32, c_void_p, c_uint32, POINTER(Stats),
+                                             POINTER(AdaptStats)]
+        L.rtx_accum_add_adaptive.restype = c_int
+        L.rtx_accum_tile_shape.argtypes = [c_void_p, POINTER(c_uint32), POINTER(c_uint32)]
+        L.rtx_accum_tile_shape.restype = c_int
+        L.rtx_accum_sample_counts_device.argtypes = [c_void_p, c_void_p, c_void_p]
+        L.rtx_accum_sample_counts_device.restype = c_int
+        L.rtx_accum_sample_counts.argtypes = [c_void_p, c_void_p]
+        L.rtx_accum_sample_counts.restype = c_int
     _lib = L
     return L
 
@@ -752,6 +771,38 @@ class Accumulator:
         check(load().rtx_accum_add(self._h, count, c_void_p(stream), flags | (RTX_FLAG_COUNTERS if counters else 0),
                                    ctypes.byref(st) if st is not None else None), "rtx_accum_add")
         return st
+
+    def add_adaptive(self, count: int, rel_tol: float, min_samples: int = 1, stream: int = 0, stats: bool = True,
+                     counters: bool = False, flags: int = 0):
+        """rtx_accum_add_adaptive: close the open tiles without a noisy pixel at rel_tol (once min_samples have been
+        offered), then `count` samples for the pixels of the tiles still open.  Returns (Stats, AdaptStats) after
+        waiting (AdaptStats.open_tiles == 0: nothing was sampled, stop), or (None, None) with stats=False (enqueued)."""
+        want = stats or counters
+        st, ad = (Stats(), AdaptStats()) if want else (None, None)
+        check(load().rtx_accum_add_adaptive(self._h, count, rel_tol, min_samples, c_void_p(stream),
+                                            flags | (RTX_FLAG_COUNTERS if counters else 0),
+                                            ctypes.byref(st) if want else None, ctypes.byref(ad) if want else None),
+              "rtx_accum_add_adaptive")
+        return st, ad
+
+    @property
+    def tile_shape(self):
+        """rtx_accum_tile_shape: (width, height) of the tiles an adaptive pass opens and closes."""
+        w, h = c_uint32(), c_uint32()
+        check(load().rtx_accum_tile_shape(self._h, ctypes.byref(w), ctypes.byref(h)), "rtx_accum_tile_shape")
+        return int(w.value), int(h.value)
+
+    def sample_counts_device(self, counts_ptr: int, stream: int = 0) -> None:
+        """rtx_accum_sample_counts_device: uint32 [rows, width] into device memory, the samples each pixel received."""
+        check(load().rtx_accum_sample_counts_device(self._h, c_void_p(counts_ptr), c_void_p(stream)),
+              "rtx_accum_sample_counts_device")
+
+    def sample_counts(self):
+        """rtx_accum_sample_counts: uint32 [rows, width], the samples each pixel received.  Blocking."""
+        import numpy as np
+        out = np.zeros((self.rows, self.width), dtype=np.uint32)
+        check(load().rtx_accum_sample_counts(self._h, out.ctypes.data_as(c_void_p)), "rtx_accum_sample_counts")
+        return out
 
     @property
     def samples(self) -> int:
