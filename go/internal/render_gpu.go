@@ -665,6 +665,115 @@ func ScatterBatch(world Hittable, rays []Ray, hits []HitInfo, keys []PathKey, se
 	return out, nil
 }
 
+// Light is one row of the emitter table (rtx_light, rtx.h "direct light sampling"): Quad says which table Index
+// names (the flattener's sphere or quad numbering), Area is the float32 area the light sample divides by.
+type Light struct {
+	Quad  bool
+	Index uint32
+	Area  float32
+}
+
+// Lights is the emitter table of a world (rtx_scene_lights): its referenced DiffuseLight spheres, then quads.  The
+// world is flattened and uploaded for the call, as in HitBatch (rtx_lights answers from a description alone).
+func Lights(world Hittable) ([]Light, error) {
+	scene, _, err := sceneTables(world, 0)
+	if errors.Is(err, errUnsupported) {
+		return nil, errFallback
+	}
+	if err != nil {
+		return nil, err
+	}
+	defer C.rtx_scene_destroy(scene)
+	var n C.uint32_t
+	if rc := C.rtx_scene_lights(scene, nil, 0, &n); rc != 0 {
+		return nil, rtxErr(rc)
+	}
+	out := make([]Light, int(n))
+	if n == 0 {
+		return out, nil
+	}
+	tab := make([]C.rtx_light, int(n))
+	if rc := C.rtx_scene_lights(scene, &tab[0], n, &n); rc != 0 {
+		return nil, rtxErr(rc)
+	}
+	for i := range out {
+		var l C.rtx_light = tab[i]
+		out[i] = Light{Quad: uint32(l.prim)>>28 == C.RTX_PRIM_QUAD, Index: uint32(l.prim) & 0x0FFFFFFF, Area: float32(l.area)}
+	}
+	return out, nil
+}
+
+// DirectSample is one light sample at a Lambertian hit and its shadow ray's answer (rtx_direct_sample): Radiance is
+// (albedo * emitted) * Geom WITHOUT the visibility, which the caller applies: L += T * Radiance when Visible.
+type DirectSample struct {
+	Sampled, Visible bool
+	Radiance         Vec3
+	Shadow           Ray // to be hit with Interval{0.001, 0.999}
+	Light, Draws     uint32
+	Geom             float32
+}
+
+// DirectBatch samples one emitter point per hit and walks the shadow ray to it on the GPU (rtx_direct): hits[i] as
+// HitBatch returned it, keys[i] the key of the scatter at that hit, seed the RNG contract's seed.  The world is
+// flattened and uploaded for the call, as in HitBatch.
+func DirectBatch(world Hittable, hits []HitInfo, keys []PathKey, seed uint64) ([]DirectSample, error) {
+	if len(hits) != len(keys) {
+		return nil, errors.New("rtx: DirectBatch needs one key per hit")
+	}
+	out := make([]DirectSample, len(hits))
+	if len(hits) == 0 {
+		return out, nil
+	}
+	scene, t, err := sceneTables(world, 0)
+	if errors.Is(err, errUnsupported) {
+		return nil, errFallback
+	}
+	if err != nil {
+		return nil, err
+	}
+	defer C.rtx_scene_destroy(scene)
+	n := uintptr(len(hits))
+	hitBuf, hitPtr := alignedBytes(n * unsafe.Sizeof(C.rtx_hit{}))
+	keyBuf, keyPtr := alignedBytes(n * unsafe.Sizeof(C.rtx_path_key{}))
+	outBuf, outPtr := alignedBytes(n * unsafe.Sizeof(C.rtx_direct_sample{}))
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pin.Pin(&hitBuf[0])
+	pin.Pin(&keyBuf[0])
+	pin.Pin(&outBuf[0])
+	inHits, inKeys, samples := (*C.rtx_hit)(hitPtr), (*C.rtx_path_key)(keyPtr), (*C.rtx_direct_sample)(outPtr)
+	chits, ckeys := unsafe.Slice(inHits, len(hits)), unsafe.Slice(inKeys, len(hits))
+	for i := range hits {
+		ckeys[i] = C.rtx_path_key{pixel: C.uint32_t(keys[i].Pixel), sample: C.uint32_t(keys[i].Sample), event: C.uint32_t(keys[i].Event)}
+		chits[i] = C.rtx_hit{t: C.float(math.Inf(1)), prim: C.RTX_HIT_NONE}
+		mi, known := t.matIdx[hits[i].material]
+		if hits[i].material == nil || !known {
+			continue
+		}
+		front := C.uint32_t(0)
+		if hits[i].frontFace {
+			front = 1
+		}
+		// (prim only says "a hit" to rtx_direct: the material index, the point and the normal are what it reads)
+		chits[i] = C.rtx_hit{t: C.float(hits[i].t), prim: 0, material: mi, front_face: front, point: vec(hits[i].point),
+			u: C.float(hits[i].u), normal: vec(hits[i].normal), v: C.float(hits[i].v)}
+	}
+	if rc := C.rtx_direct(scene, C.uint64_t(seed), inHits, inKeys, C.uint64_t(len(hits)), samples, 0, nil); rc != 0 {
+		if gpuMissing(rc) {
+			return nil, errFallback
+		}
+		return nil, rtxErr(rc)
+	}
+	v3 := func(a [3]C.float) Vec3 { return NewVec3(float32(a[0]), float32(a[1]), float32(a[2])) }
+	for i, rec := range unsafe.Slice(samples, len(hits)) {
+		var d C.rtx_direct_sample = rec
+		out[i] = DirectSample{Sampled: d.flags&C.RTX_DIRECT_SAMPLED != 0, Visible: d.flags&C.RTX_DIRECT_VISIBLE != 0,
+			Radiance: v3(d.radiance), Shadow: Ray{origin: v3(d.ray.origin), dir: v3(d.ray.dir)},
+			Light: uint32(d.light), Draws: uint32(d.rng_draws), Geom: float32(d.geom)}
+	}
+	return out, nil
+}
+
 // gpuCamera is Camera.init's derived state (camera.go:128-165) as rtx.h's kernel constants.
 func (c *Camera) gpuCamera() C.rtx_camera {
 	return C.rtx_camera{
@@ -730,6 +839,45 @@ func (c *Camera) RenderProgressive(world Hittable, writer io.Writer, passSamples
 		return rtxErr(rc)
 	}
 	if rc := C.rtx_device_check(0); rc != 0 { // the passes ran without stats: the sticky error word, once
+		return rtxErr(rc)
+	}
+	_, err = writer.Write(text[:int(n)])
+	return err
+}
+
+// RenderDirect is Render with direct light sampling (rtx_accum_add_direct, rtx.h "direct light sampling"): every
+// sample by the next-event estimator, in passes of passSamples (<= 0: one pass).  Same mean as Render, another image;
+// a world without emitters gives Render's own image.
+func (c *Camera) RenderDirect(world Hittable, writer io.Writer, passSamples int) error {
+	c.init()
+	cfg := c.gpuConfig()
+	if passSamples <= 0 {
+		passSamples = c.samplesPerPixel
+	}
+	scene, err := sceneOf(world, cfg.seed)
+	if err != nil {
+		return err
+	}
+	defer C.rtx_scene_destroy(scene) // (deferred calls run last in, first out: the accumulator goes first)
+	cam := c.gpuCamera()
+	region := C.rtx_region{x0: 0, y0: 0, width: cam.image_width, height: cam.image_height, rank: 0, world: 1, stripe: 0}
+	var acc *C.rtx_accum
+	if rc := C.rtx_accum_create(scene, &cam, C.uint64_t(cfg.seed), &region, &acc); rc != 0 {
+		return rtxErr(rc)
+	}
+	defer C.rtx_accum_destroy(acc)
+	for done := 0; done < c.samplesPerPixel; done = int(C.rtx_accum_samples(acc)) {
+		count := min(passSamples, c.samplesPerPixel-done)
+		if rc := C.rtx_accum_add_direct(acc, C.uint32_t(count), nil, 0, nil); rc != 0 {
+			return rtxErr(rc)
+		}
+	}
+	text := make([]byte, int(C.rtx_ppm_max_bytes(cam.image_width, cam.image_height)))
+	var n C.uint64_t
+	if rc := C.rtx_accum_ppm(acc, (*C.char)(unsafe.Pointer(&text[0])), C.uint64_t(len(text)), &n); rc != 0 {
+		return rtxErr(rc)
+	}
+	if rc := C.rtx_device_check(0); rc != 0 {
 		return rtxErr(rc)
 	}
 	_, err = writer.Write(text[:int(n)])

@@ -911,6 +911,123 @@ int rtx_accum_preview(rtx_accum* accum, uint32_t guide_samples, const rtx_denois
 int rtx_accum_preview_ppm(rtx_accum* accum, uint32_t guide_samples, const rtx_denoise_params* params, char* out_text,
                           uint64_t capacity, uint64_t* out_len);
 
+/* ---- direct light sampling (ABI 10, additive) ----------------------
+ * Ray.GetColor finds a DiffuseLight only when a bounce happens to hit it (ray.go:41-47).  Next-event estimation
+ * samples a point on an emitter at a diffuse hit and casts a shadow ray to it.  This section gives the emitter table
+ * and the BLOCK that does both for a batch of hits; it composes with rtx_trace* and rtx_shade* (wavefront.py's
+ * render(direct=True) is the estimator).  Every render, pass and image of the other sections is what it was.
+ *
+ * The emitter table.  The emitters are the spheres and quads the world references (roots, nodes, lists) whose
+ * material is RTX_MAT_DIFFUSE_LIGHT: spheres in sphere-table order, then quads in quad-table order, each once.  A
+ * primitive the tree never references is not an emitter; nor is a sphere with radius <= 0, nor an emitter whose area
+ * is not finite and > 0.  Areas are float32:
+ *   sphere:  area = (4 * PiF32) * (r * r)          (PiF32 = float32(math.Pi), math.go:48)
+ *   quad:    area = Len(Cross(u, v))               (vec3.go:119-135; the square root goes through float64, as Len's)
+ * L is the count; a scene with L > 2^24 is refused (RTX_ERR_INVALID_ARG): (float)L must be exact.  The table is built
+ * on the host and uploaded by the first call that needs it, as the trace layout is. */
+typedef struct rtx_light { /* 8 B */
+    uint32_t prim; /* type << 28 | index into the CALLER's sphere / quad table, as rtx_hit.prim */
+    float area;
+} rtx_light;
+/* The table of a scene description (validated as rtx_scene_create does), without a scene or a device, or of a scene:
+ * *n = L; out is filled when cap >= L (out may be NULL to ask for the count).  Host only. */
+int rtx_lights(const rtx_scene_desc* desc, rtx_light* out, uint32_t cap, uint32_t* n);
+int rtx_scene_lights(const rtx_scene* scene, rtx_light* out, uint32_t cap, uint32_t* n);
+
+/* The block.  Record i takes d_hits[i], the CLOSEST hit rtx_trace* wrote with RTX_TRACE_UV, the rtx_path_key of the
+ * scatter at that hit (d_keys[i]) and the render's seed, and gives one light sample and its shadow ray's answer.
+ * One kernel does both halves: the sample by the render's own device functions (the four textures, the sphere UV,
+ * the unit-sphere loop), the shadow walk over the ray queries' layouts.  The arithmetic is the contract: float32,
+ * every operation rounded on its own, no fused multiply-add; Dot, Len, Cross as vec3.go states them.
+ *
+ *   only when hit.prim != RTX_HIT_NONE, hit.material indexes a Lambertian and L > 0; otherwise the record is all zero
+ *   p = hit.point   n = hit.normal   a = the Lambertian's texture at (hit.u, hit.v, p)
+ *   B0 = Philox block (pixel, sample, 0x40000000 | event, 0)     (the light events of DESIGN.md §3; unit(w) =
+ *                                                                 (float)(w >> 8) * 2^-24, rand.Float32's)
+ *   j  = min((uint32)(unit(B0.x) * (float)L), L - 1)
+ *   quad j:    x1 = unit(B0.y), x2 = unit(B0.z);  q = (Q + x1 * u) + x2 * v;  nl = the quad's normal;  (lu, lv) = (x1, x2)
+ *   sphere j:  d = the loop of vec3.go:182-190, attempt a = 1, 2, .. taking words 0-2 of block (.., 0x40000000 | event, a)
+ *              q = c + r * d;  nl = d;  (lu, lv) = the sphere UV of d (hittables.go:122-126)
+ *   w = q - p;  d2 = Dot(w, w);  dist = Len(w);  cs = Dot(n, w) / dist;  cl = |Dot(nl, w)| / dist
+ *   SAMPLED = d2 > 0 && cs > 0 && cl > 0           (a NaN fails; DiffuseLight.Emit ignores the face: both sides emit)
+ *   g  = (((cs * cl) * area_j) * (float)L) / (PiF32 * d2)
+ *   Le = the emitter's texture at (lu, lv, q), all four texture kinds
+ *   radiance_c = (a_c * Le_c) * g
+ *   ray = { origin p, tmin 0.001f, dir w, tmax 0.999f }
+ *   VISIBLE = SAMPLED && no primitive accepted on ray   (exactly rtx_trace(ray, RTX_TRACE_ANY).prim == RTX_HIT_NONE)
+ *
+ * g is the Lambertian BRDF (a / pi) times the geometry term cs * cl / d2 over the density 1 / (L * area_j) of the
+ * point q.  radiance does NOT include the visibility: the caller adds it when RTX_DIRECT_VISIBLE is set.  A record
+ * that is not SAMPLED has `light` and `rng_draws` filled and every other field zero.
+ * The sphere case samples its whole area uniformly: half of the points face away from p, and the shadow ray then
+ * finds the sphere's own near side (tmax 0.999 ends before q, tmin 0.001 starts past p).  That is unbiased and
+ * wasteful.  Not provided: cone sampling of spheres, power-proportional light selection, multiple importance
+ * sampling with the bounce.
+ * Argument checks (before any device is touched), alignment, n == 0, the scene's mutex, the 32-bit launch cut, the
+ * counters and events of its own and the untouched sample scratch are rtx_shade_device's.  Input and output buffers
+ * must not overlap. */
+typedef struct rtx_direct_sample { /* 64 B */
+    float radiance[3];  /* (a * Le) * g, visibility NOT applied; 0 when not SAMPLED                  */
+    uint32_t flags;     /* RTX_DIRECT_SAMPLED | RTX_DIRECT_VISIBLE                                   */
+    rtx_ray ray;        /* the shadow ray; all zero when not SAMPLED                                  */
+    uint32_t light;     /* j, the index into the emitter table                                        */
+    uint32_t rng_draws; /* rand.Float32() calls: 1 + 2 for a quad, 1 + 3 per attempt for a sphere      */
+    float geom;         /* g                                                                          */
+    uint32_t reserved;  /* 0                                                                          */
+} rtx_direct_sample;
+#define RTX_DIRECT_SAMPLED 1u
+#define RTX_DIRECT_VISIBLE 2u
+#define RTX_DIRECT_COUNTERS 1u /* counting instantiation: sampled, visible, rng_draws (with stats only) */
+typedef struct rtx_direct_stats {
+    uint64_t n;         /* records                                                    */
+    uint64_t sampled;   /* RTX_DIRECT_COUNTERS: records with RTX_DIRECT_SAMPLED       */
+    uint64_t visible;   /* RTX_DIRECT_COUNTERS: records with RTX_DIRECT_VISIBLE       */
+    uint64_t rng_draws; /* RTX_DIRECT_COUNTERS: the sum of rtx_direct_sample.rng_draws       */
+    double kernel_ms;   /* device time of the launches, HIP events on the stream      */
+} rtx_direct_stats;
+
+/* Records in device memory of the CURRENT device, on the given HIP stream.  Returns after enqueueing unless
+ * stats != NULL; then it synchronises the stream and fills stats.  The emitter table and the trace layout are
+ * uploaded by the first call that needs them (blocking copies). */
+int rtx_direct_device(rtx_scene* scene, uint64_t seed, const rtx_hit* d_hits, const rtx_path_key* d_keys, uint64_t n,
+                      rtx_direct_sample* d_out, uint32_t flags, void* hip_stream, rtx_direct_stats* stats);
+/* The same for records in host memory, on the current device.  Blocking. */
+int rtx_direct(rtx_scene* scene, uint64_t seed, const rtx_hit* hits, const rtx_path_key* keys, uint64_t n,
+               rtx_direct_sample* out, uint32_t flags, rtx_direct_stats* stats);
+
+/* The estimator and the fused pass.  Ray.GetColor (ray.go:32-54) with one change: radiance a Lambertian bounce would
+ * have found by hitting an emitter is taken from the block instead.  Per sample L = 0, T = 1, diffuse = false; for
+ * segment s = 0 .. max_depth - 1, in this order, every * and + rounded on its own:
+ *
+ *   miss:  L += T * background; end
+ *   hit:   if EMITS and !diffuse:                       L += T * emitted
+ *          lam = SCATTERED and the material is Lambertian
+ *          if lam and s + 1 < max_depth and L_lights > 0:
+ *              d = direct(hit, key(event s + 1));  if d.VISIBLE:  L += T * d.radiance
+ *          if !SCATTERED: end
+ *          T *= attenuation;  diffuse = lam and L_lights > 0;  continue with the bounce ray
+ *
+ * s + 1 < max_depth keeps the set of path lengths the reference's depth cap allows, so the expectation is the plain
+ * render's; with no emitter nothing is added and nothing suppressed, and the pass computes the plain render, bit for
+ * bit.  CAVEAT of the rule: `diffuse` also drops the emission of a DiffuseLight primitive the emitter table excludes
+ * (zero area, radius <= 0) when the scene has other emitters: biased for such a primitive, which the reference renders.
+ *
+ * rtx_accum_add_direct renders samples n .. n + count - 1 of every pixel this way in one kernel (no ray, hit, bounce
+ * or path state goes through memory) and folds S += c; Q += c * c in k order, as rtx_accum_add does; its image equals
+ * rtx_camera_rays -> (rtx_trace(RTX_TRACE_UV) -> rtx_shade -> rtx_direct) x max_depth composed as above, bit for bit on
+ * a scene that keeps the caller's tree (on the library's own trees up to the grazing hits of DESIGN.md §12).
+ * An accumulator is plain, adaptive or direct from its first pass until rtx_accum_reset: rtx_accum_add or
+ * rtx_accum_add_adaptive after a direct pass, and rtx_accum_add_direct after either of them, return
+ * RTX_ERR_INVALID_ARG, as do a NULL accumulator, count == 0, n + count past 2^32 - 1 and flags != 0, all before any
+ * device is touched.  Returns after enqueueing unless stats != NULL; then it synchronises and fills samples,
+ * sample_chunks, kernel_ms and walk_layout of this pass.  Resolve, ppm, preview and sample_counts read a direct
+ * accumulator as they read a plain one.  The pass uses none of the sample scratch.
+ * Tuning knobs, read from the environment per call, none of which changes a bit of any output: RTX_DIRECT_RANGE
+ * (records per wave of the block, 256), RTX_DIRECT_REFILL (parked lanes at which a wave of the pass runs its fold step,
+ * 32), RTX_DIRECT_PRIM_BATCH (lanes a primitive test waits for, 16), RTX_DIRECT_LAUNCH_RECORDS (records per launch of
+ * the block: tests of the cut). */
+int rtx_accum_add_direct(rtx_accum* accum, uint32_t count, void* hip_stream, uint32_t flags, rtx_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ struct rtx_accum {
     // last selection, then one word per tile (0: open, else the n it closed at), then the list of open tiles
     rtxd::DeviceBuffer adapt;
     bool adaptive = false;  // an adaptive pass since create / reset: the tiles no longer share one n
+    bool direct = false;    // a direct-light pass since create / reset: another estimator's samples
     uint32_t n = 0;         // the frontier: the samples offered so far
     float* s() const { return sums.as<float>(); }
     float* q() const { return s() + slots * 3; }
@@ -144,6 +145,7 @@ int rtx_accum_add(rtx_accum* a, uint32_t count, void* hip_stream, uint32_t flags
     if (a->n + count < a->n) return fail(RTX_ERR_INVALID_ARG, "%u + %u samples exceed 2^32 - 1", a->n, count);
     if (a->adaptive)
         return fail(RTX_ERR_INVALID_ARG, "a uniform pass after an adaptive one: the tiles no longer share one n (reset first)");
+    if (a->direct) return fail(RTX_ERR_INVALID_ARG, "a plain pass after a direct-light one: another estimator (reset first)");
     if (int rc = accum_device(a)) return rc;
     rtx_scene* s = a->scene;
     std::lock_guard<std::mutex> lk(s->mu);
@@ -169,6 +171,7 @@ int rtx_accum_add_adaptive(rtx_accum* a, uint32_t count, float rel_tol, uint32_t
     if (count == 0) return fail(RTX_ERR_INVALID_ARG, "a pass of 0 samples");
     if (a->n + count < a->n) return fail(RTX_ERR_INVALID_ARG, "%u + %u samples exceed 2^32 - 1", a->n, count);
     if (!(rel_tol >= 0.0f)) return fail(RTX_ERR_INVALID_ARG, "rel_tol %g: a tolerance is >= 0", (double)rel_tol);
+    if (a->direct) return fail(RTX_ERR_INVALID_ARG, "an adaptive pass after a direct-light one: another estimator (reset first)");
     if (int rc = accum_device(a)) return rc;
     rtx_scene* s = a->scene;
     hipStream_t st = (hipStream_t)hip_stream;
@@ -211,6 +214,32 @@ int rtx_accum_add_adaptive(rtx_accum* a, uint32_t count, float rel_tol, uint32_t
     const int rc = collect_on(c, (flags & RTX_FLAG_COUNTERS) != 0, (uint64_t)h.open_pixels * count, chunks, stats);
     stats->walk_layout = walk_layout(s, &a->cam, tiered);
     return rc;
+}
+
+int rtx_accum_add_direct(rtx_accum* a, uint32_t count, void* hip_stream, uint32_t flags, rtx_stats* stats) {
+    g_last_error.clear();
+    if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
+    if (count == 0) return fail(RTX_ERR_INVALID_ARG, "a pass of 0 samples");
+    if (a->n + count < a->n) return fail(RTX_ERR_INVALID_ARG, "%u + %u samples exceed 2^32 - 1", a->n, count);
+    if (flags != 0u) return fail(RTX_ERR_INVALID_ARG, "direct pass flags 0x%x: must be 0", flags);
+    if (a->adaptive) return fail(RTX_ERR_INVALID_ARG, "a direct-light pass after an adaptive one (reset first)");
+    if (a->n != 0u && !a->direct)
+        return fail(RTX_ERR_INVALID_ARG, "a direct-light pass after a plain one: another estimator (reset first)");
+    if (int rc = accum_device(a)) return rc;
+    rtx_scene* s = a->scene;
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceCopy* c = nullptr;
+    if (int rc = ensure_device(s, a->device, &c)) return rc;
+    if (a->slots != 0) {  // (an empty shard: nothing to render)
+        if (int rc = direct_pass_locked(s, &a->cam, a->seed, &a->region, a->tile_w_log2, a->n, count, a->s(), a->q(),
+                                        (hipStream_t)hip_stream, stats))
+            return rc;
+    } else if (stats) {
+        *stats = rtx_stats{};
+    }
+    a->direct = true;
+    a->n += count;
+    return RTX_OK;
 }
 
 uint32_t rtx_accum_samples(const rtx_accum* a) { return a ? a->n : 0u; }
@@ -373,6 +402,7 @@ int rtx_accum_reset(rtx_accum* a) {
     HIP_TRY(hipMemset(a->sums.ptr, 0, a->sums.bytes));
     HIP_TRY(hipMemset(a->adapt.ptr, 0, a->adapt.bytes));  // every tile open again
     a->adaptive = false;
+    a->direct = false;
     a->n = 0;
     return RTX_OK;
 }

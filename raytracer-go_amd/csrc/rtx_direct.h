@@ -1,0 +1,71 @@
+// rtx_direct.h — launch interface between the C-ABI layer and the direct-light block (rtx_direct.hip):
+// rtx_direct_device / rtx_direct of include/rtx.h, DESIGN.md §37.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/rtx.h"
+
+namespace rtxd {
+// Device counters of a counting call, in memory of the scene copy's own (never the render's, the trace's or the shade's).
+constexpr uint32_t DIRECT_SAMPLED = 0u, DIRECT_VISIBLE = 1u, DIRECT_RNG_DRAWS = 2u, DIRECT_COUNTER_SLOTS = 3u;
+
+// The light events of the Philox counter: word 2 = DIRECT_EVENT | the scatter's event.
+constexpr uint32_t DIRECT_EVENT = 0x40000000u;
+
+// One launch: records [0, n) of the three arrays, n <= DIRECT_LAUNCH_MAX (record indices are 32-bit).
+constexpr uint64_t DIRECT_LAUNCH_MAX = 1ull << 30;
+struct DirectParams {
+    const float4* entries;  // a trace layout (rtx_layout.h): n_entries + 1 'a' halves, as many 'b', 4 * n_quads
+    uint32_t n_entries;
+    uint32_t n_quads;
+    uint32_t start;     // walk position of the root
+    uint32_t prim_end;  // scene in the LDS copy: its primitives are stored below this position
+    const rtx_material* materials;  // the device forms of DeviceCopy
+    const rtx_texture* textures;
+    const uint32_t* texels;
+    uint32_t n_materials;
+    uint32_t n_lights;     // L; 0: every record is all zero
+    const float4* lights;  // 4 per emitter (build_lights, rtx_scene.hip)
+    uint64_t seed;
+    const rtx_hit* hits;
+    const rtx_path_key* keys;
+    rtx_direct_sample* out;
+    uint32_t n;
+    uint32_t range;       // records per wave, a multiple of 64: wave w owns records [w * range, (w + 1) * range)
+    uint32_t prim_batch;  // primitive tests wait for this many lanes (trav_step_batched)
+    unsigned long long* counters;  // DIRECT_COUNTER_SLOTS, the counting instantiation
+};
+// Enqueue one launch on `stream`.  count: the counting instantiation (adds to p.counters); noise: the scene has a
+// Perlin texture.
+hipError_t launch_direct(const DirectParams& p, bool count, bool noise, hipStream_t stream);
+
+// One launch of the fused pass (rtx_accum_add_direct, direct_paths): samples [k0, k0 + kn) of the region's
+// width * rows pixels (at most 2^32 - 1) by the estimator of DESIGN.md §37, folded into the accumulator's tile-major
+// moments acc_s and acc_q (slot = tile * 64 + lane, 3 floats each; rtx_kernel.hip accumulate_samples' layout).
+struct DirectPathParams {
+    rtx_camera cam;
+    uint64_t seed;
+    uint32_t x0, y0, width, rows, rank, world, stripe_log2;
+    uint32_t k0, kn;
+    uint32_t tile_w_log2;   // the accumulator's tiles: 2^tile_w_log2 wide, 64 pixels
+    const float4* entries;  // a trace layout (rtx_layout.h), as TraceParams'
+    uint32_t n_entries;
+    uint32_t n_quads;
+    uint32_t start;
+    uint32_t prim_end;
+    uint32_t refill;        // parked lanes with work at which a wave runs its fold step (1..64)
+    uint32_t prim_batch;    // primitive tests wait for this many lanes (trav_step_batched)
+    uint32_t want_uv;       // the scene has an image texture: sphere hits need (u, v)
+    const rtx_material* materials;
+    const rtx_texture* textures;
+    const uint32_t* texels;
+    uint32_t n_materials;
+    uint32_t n_lights;
+    const float4* lights;
+    float* acc_s;
+    float* acc_q;
+};
+// Enqueue one launch on `stream`.  noise: the scene has a Perlin texture.
+hipError_t launch_direct_paths(const DirectPathParams& p, bool noise, hipStream_t stream);
+}  // namespace rtxd

@@ -1,0 +1,558 @@
+// rtx_direct.hip — direct light sampling for a batch of hits (rtx_direct_device): one light sample per
+// record and the answer of its shadow ray, in one kernel.
+//
+//   sample   the contract of include/rtx.h ("direct light sampling"), computed with the render's own device functions
+//            (rtx_device.h: the Philox block, texture_value, sphere_uv, unit, and the unit-sphere loop of
+//            rand_unit_on_sphere with its attempts on blocks 1, 2, ..): float32, each operation rounded, no contraction.
+//   shadow   trace_rays' any-hit walk (rtx_trace.hip) over the same trace layout: trav_begin, then the batched step with
+//            the ray's own tmin and the bound starting at tmax = 0.999, a lane parking at its first accepted primitive.
+//
+// Work distribution: no cross-wave state.  Wave w owns records [w * range, (w + 1) * range) and takes them 64 at a
+// time, the plain form of trace_rays (refill = 64): the block's samples are computed, its shadow rays are walked
+// until every lane is parked on the end sentinel, the 64 records are stored.  A lane past the end of the range
+// computes on the range's last record and stores nothing; a lane without a shadow ray starts parked.  Walk positions
+// only move forward and the range is finite, so both loops end; nothing spins.  The only atomics are the counting
+// instantiation's: one per wave and counter, after the wave's last block.
+//
+// Wave votes.  The ballots here, in trav_begin and in the batched step sit where the whole wave arrives.  unit()'s
+// reciprocal and square root and the checker's parity (texture_value) are reached under a lane's own branch, as in
+// shade_hits (rtx_shade.hip): both of their forms return the same bits for every lane the short form admits, and a
+// ballot only sees the lanes that are there.
+#include "rtx_direct.h"
+
+#include "rtx_device.h"
+#include "rtx_trace.h"
+
+namespace rtxd {
+namespace {
+
+constexpr int DIRECT_WAVES = 8;        // waves per workgroup (one LDS copy of the scene each)
+constexpr uint32_t DIRECT_STEPS = 4;   // walk steps between two votes on the parked lanes
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+    return v;
+}
+
+// What a light sample reads of the scene copy.
+struct LightTables {
+    const rtx_material* materials;
+    const rtx_texture* textures;
+    const uint32_t* texels;
+    const float4* lights;
+    uint32_t n_lights;
+};
+
+// The texture of a Lambertian or a DiffuseLight (device material m0, m1) at (u, v, pt).
+template <bool NOISE>
+__device__ __forceinline__ V3 material_colour(const LightTables& p, const float4 m0, const float4 m1, float u, float v,
+                                              V3 pt) {
+    const uint32_t tex = __float_as_uint(m0.y);
+    if (tex == RTX_DEV_TEX_INLINE) return v3(m1.x, m1.y, m1.z);  // a SolidColor, the colour in albedo
+    Counters cnt{0, 0, 0, 0, 0, 0, 0};
+    return texture_value<false, NOISE>(p.textures, p.texels, tex, u, v, pt, cnt);
+}
+
+// One light sample (the contract of rtx.h, "direct light sampling") at the Lambertian hit (pt, n, u, v) of device
+// material (m0, m1), for the lanes with `lam`; b0 is block (e, 0) of the light event e, drawn by every lane.
+struct LightSample {
+    bool sampled;
+    uint32_t j, draws;
+    float g;
+    V3 rad, w;  // (a * Le) * g; q - p, the shadow ray's direction
+};
+template <bool NOISE>
+__device__ __forceinline__ LightSample light_sample(const LightTables& p, const bool lam, const float4 m0, const float4 m1,
+                                                    const V3 pt, const V3 n, const float hu, const float hv,
+                                                    const PathRng& rng, const uint32_t e, const U4 b0) {
+    const float pi32 = 3.14159274101257324f;  // PiF32, math.go:48
+    const float fL = (float)p.n_lights;       // exact: L <= 2^24
+    LightSample s{false, 0u, 0u, 0.0f, v3(0.0f, 0.0f, 0.0f), v3(0.0f, 0.0f, 0.0f)};
+    if (lam) {
+        const uint32_t jf = (uint32_t)(unit_f32(b0.x) * fL);
+        s.j = jf < p.n_lights - 1u ? jf : p.n_lights - 1u;
+        const float4* lp = p.lights + 4u * s.j;
+        const float4 l0 = lp[0], l1 = lp[1], l2 = lp[2], l3 = lp[3];
+        const float area = l1.w;
+        V3 q, nl;
+        float lu, lv;
+        s.draws = 1;
+        if (__float_as_uint(l2.w) == RTX_PRIM_QUAD) {
+            lu = unit_f32(b0.y);
+            lv = unit_f32(b0.z);
+            s.draws += 2;
+            q = add(add(v3(l0.x, l0.y, l0.z), scale(v3(l1.x, l1.y, l1.z), lu)), scale(v3(l2.x, l2.y, l2.z), lv));
+            nl = v3(l3.x, l3.y, l3.z);
+        } else {
+            V3 d = v3(0.0f, 0.0f, 0.0f);
+            for (uint32_t a = 1;; ++a) {  // vec3.go:182-190, attempt a on block (e, a): the per-lane rejection loop
+                const U4 b = rng.block(e, a);
+                const V3 c = v3(signed_unit(b.x), signed_unit(b.y), signed_unit(b.z));
+                s.draws += 3;
+                if (lensq(c) < 1.0f) {
+                    d = unit(c);
+                    break;
+                }
+            }
+            q = add(v3(l0.x, l0.y, l0.z), scale(d, l0.w));
+            nl = d;
+            const UV uv = sphere_uv(d.x, d.y, d.z);  // hittables.go:122-126
+            lu = uv.u;
+            lv = uv.v;
+        }
+        s.w = sub(q, pt);
+        const float d2 = dot(s.w, s.w);
+        const float dist = (float)__builtin_sqrt((double)d2);  // vec3.go:119-121
+        const float cs = dot(n, s.w) / dist;
+        const float cl = __builtin_fabsf(dot(nl, s.w)) / dist;
+        s.sampled = d2 > 0.0f && cs > 0.0f && cl > 0.0f;  // (a NaN fails)
+        if (s.sampled) {
+            s.g = (((cs * cl) * area) * fL) / (pi32 * d2);
+            const V3 a = material_colour<NOISE>(p, m0, m1, hu, hv, pt);
+            const float4* ep = reinterpret_cast<const float4*>(p.materials + __float_as_uint(l3.w));
+            const V3 le = material_colour<NOISE>(p, ep[0], ep[1], lu, lv, q);
+            s.rad = scale(mul(a, le), s.g);
+        }
+    }
+    return s;
+}
+
+// COUNT: the counting instantiation (sampled, visible, rng_draws).  QUADS: the scene holds quads.  FIXED: the scene
+// in the workgroup's LDS copy (scene_ref_fixed), else read from HBM.  NOISE: the scene has a Perlin texture.
+template <bool COUNT, bool QUADS, bool FIXED, bool NOISE>
+__global__ __launch_bounds__(64 * DIRECT_WAVES) void direct_lights(DirectParams p) {
+    extern __shared__ float4 lds_entries[];
+    SceneRef E;
+    if constexpr (FIXED) {
+        // scene_ref_fixed: the walk addresses LDS directly, so the copy must start at 0
+        if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) float4*)lds_entries != 0u) __builtin_trap();
+        const uint32_t m = p.n_entries + 1, nq4 = 4 * p.n_quads;
+        for (uint32_t i = threadIdx.x; i < m; i += 64 * DIRECT_WAVES) {
+            lds_entries[i] = p.entries[i];
+            lds_entries[LDS_B / 16 + i] = p.entries[m + i];
+        }
+        for (uint32_t i = threadIdx.x; i < nq4; i += 64 * DIRECT_WAVES) lds_entries[LDS_B / 16 + m + i] = p.entries[2 * m + i];
+        __syncthreads();
+        E = scene_ref_fixed(lds_entries, p.n_entries, p.n_quads, 0u, 0u);
+        E.prim_end = p.prim_end;
+    } else {
+        E = scene_ref(p.entries, p.n_entries, nullptr);
+    }
+    const uint32_t end = 16 * p.n_entries;  // the sentinel's position
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * DIRECT_WAVES + (threadIdx.x >> 6));
+    const uint64_t first = (uint64_t)wave * p.range;
+    if (first >= p.n) return;  // (the whole wave)
+    const uint32_t last = (uint32_t)(first + p.range < p.n ? first + p.range : p.n);  // the wave's records: [first, last)
+    const LightTables tabs{p.materials, p.textures, p.texels, p.lights, p.n_lights};
+    uint32_t n_sampled = 0, n_visible = 0, n_draws = 0;  // COUNT (per lane)
+
+    for (uint32_t blk = (uint32_t)first; blk < last; blk += 64u) {
+        const uint32_t i = blk + lane;
+        const bool live = i < last;
+        const uint32_t rec = live ? i : last - 1u;
+        // 48 + 16 B in: 3 + 1 dwordx4 loads
+        const float4* hp = reinterpret_cast<const float4*>(p.hits + rec);
+        const float4 h0 = hp[0], h1 = hp[1], h2 = hp[2];
+        const uint4 key = *reinterpret_cast<const uint4*>(p.keys + rec);
+        const uint32_t mi = __float_as_uint(h0.z);
+        // (a material index outside the table is no hit: the record comes from the caller)
+        const bool hit = live && __float_as_uint(h0.y) != RTX_HIT_NONE && mi < p.n_materials;
+        const float4* mp = reinterpret_cast<const float4*>(p.materials + (hit ? mi : 0u));
+        const float4 m0 = mp[0], m1 = mp[1];
+        const bool lam = hit && __float_as_uint(m0.x) == RTX_MAT_LAMBERTIAN && p.n_lights != 0u;
+
+        const V3 pt = v3(h1.x, h1.y, h1.z);  // HitInfo.point
+        const V3 n = v3(h2.x, h2.y, h2.z);   // HitInfo.normal: unit, against the ray
+        const PathRng rng{(uint32_t)p.seed, (uint32_t)(p.seed >> 32), key.x, key.y};
+        const uint32_t e = DIRECT_EVENT | key.z;
+        const U4 b0 = rng.block(e, 0);  // lockstep: every lane evaluates its block (e, 0) here
+
+        const LightSample ls = light_sample<NOISE>(tabs, lam, m0, m1, pt, n, h1.w, h2.w, rng, e, b0);
+        const uint32_t j = ls.j, draws = ls.draws;
+        uint32_t flags = ls.sampled ? RTX_DIRECT_SAMPLED : 0u;
+        const float g = ls.g;
+        const V3 rad = ls.rad, w = ls.w;
+        const bool sampled = ls.sampled;
+
+        // the shadow walk (the whole wave: trav_begin's votes); a lane without a shadow ray starts parked
+        const Ray r = sampled ? Ray{pt, w} : Ray{v3(0.0f, 0.0f, 0.0f), v3(1.0f, 1.0f, 1.0f)};
+        const float tmin = 0.001f;
+        Trav t;
+        trav_begin(t, r, sampled ? p.start : end);
+        t.safe = t.safe && tmin >= 0x1p-126f;  // as trace_rays: the fast step forms need every accepted root normal
+        t.closest = 0.999f;                    // the running bound starts at the ray's tmax
+        Counters cnt{0, 0, 0, 0, 0, 0, 0};
+        while (ballot(t.i < end) != 0) {
+            uint32_t idle = 0;
+            if (ballot(!t.safe && t.i < end) == 0) {
+#pragma unroll
+                for (uint32_t s = 0; s < DIRECT_STEPS; ++s) {
+                    trav_step_batched<false, QUADS, FIXED, false, true>(t, r, E, cnt, end, p.prim_batch, idle,
+                                                                        V3{0.0f, 0.0f, 0.0f}, tmin);
+                    if (t.hit >= 0) t.i = end;
+                }
+            } else {
+#pragma unroll
+                for (uint32_t s = 0; s < DIRECT_STEPS; ++s) {
+                    trav_step_batched<false, QUADS, FIXED, false, false>(t, r, E, cnt, end, p.prim_batch, idle,
+                                                                         V3{0.0f, 0.0f, 0.0f}, tmin);
+                    if (t.hit >= 0) t.i = end;
+                }
+            }
+        }
+        const bool visible = sampled && t.hit < 0;
+        if (visible) flags |= RTX_DIRECT_VISIBLE;
+
+        if (live) {  // 64 B out: four dwordx4 stores
+            const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            float4* o = reinterpret_cast<float4*>(p.out + i);
+            o[0] = make_float4(rad.x, rad.y, rad.z, __uint_as_float(flags));
+            o[1] = sampled ? make_float4(pt.x, pt.y, pt.z, tmin) : zero;
+            o[2] = sampled ? make_float4(w.x, w.y, w.z, 0.999f) : zero;
+            o[3] = make_float4(__uint_as_float(j), __uint_as_float(draws), g, 0.0f);
+        }
+        if (COUNT) {
+            n_sampled += sampled ? 1u : 0u;
+            n_visible += visible ? 1u : 0u;
+            n_draws += live ? draws : 0u;
+        }
+    }
+    if (COUNT) {  // reduced in the wave (every lane is here): one atomic per wave and counter
+        const uint32_t ns = wave_sum(n_sampled), nv = wave_sum(n_visible), nd = wave_sum(n_draws);
+        if (lane == 0u) {
+            if (ns) atomicAdd(&p.counters[DIRECT_SAMPLED], (unsigned long long)ns);
+            if (nv) atomicAdd(&p.counters[DIRECT_VISIBLE], (unsigned long long)nv);
+            if (nd) atomicAdd(&p.counters[DIRECT_RNG_DRAWS], (unsigned long long)nd);
+        }
+    }
+}
+
+// ---- the fused pass (rtx_accum_add_direct) ----------------------------------------------------------------------
+// direct_paths is guide_images' loop (rtx_guides.hip) carried through a whole path.  A wave owns one 64-pixel tile of the
+// accumulator's S / Q layout and a lane owns a pixel.  A lane's walk is either a closest-hit walk (a path segment) or a
+// shadow walk; a lane whose walk has ended is parked on the end sentinel.  Once `refill` lanes are parked with work (or
+// no lane walks) the whole wave runs one FOLD STEP: every lane forms the hit record of its walk as write_hit does
+// (rtx_trace.hip), shades it with shade_hits' per-record code (rtx_shade.hip) and samples a light (light_sample); the
+// parked lanes then apply the estimator of DESIGN.md §37 to their own result and start the shadow ray, or the bounce
+// ray when nothing was sampled, or the next sample's camera ray; a parked shadow walk adds or drops its radiance and
+// starts the saved bounce.  No ray, hit, bounce or path state goes through memory; no atomics; nothing spins (samples,
+// segments and walk positions only move forward); every vote (here, in trav_begin, unit, the batched step) sits where
+// the whole wave arrives, except those inside a lane's own material branch, as in shade_hits.
+struct PathHit {
+    bool hit, front;
+    uint32_t mi;
+    V3 pt, n;
+    float u, v;
+};
+
+// NewHitInfo of a lane's finished closest walk, as write_hit forms it (computed by every lane: unit's votes).
+template <bool QUADS>
+__device__ __forceinline__ PathHit path_hit(const SceneRef E, const Trav& t, const Ray& r, const bool want_uv) {
+    PathHit h;
+    h.hit = t.hit >= 0;
+    const uint32_t e = h.hit ? (uint32_t)t.hit : 0u;  // (a miss reads entry 0 and drops it)
+    const float4 sa = E.a[e];
+    const float4 sb = E.b[e];
+    const bool quad = QUADS && h.hit && __float_as_int(sb.w) == RTX_E_QUAD;
+    h.pt = add(scale(r.d, t.closest), r.o);                                      // ray.go:25-30
+    const V3 ns = unit(scale(sub(h.pt, v3(sa.x, sa.y, sa.z)), sa.w));            // hittables.go:119-120
+    h.n = ns;
+    h.mi = 0u;
+    h.u = h.v = 0.0f;
+    if (quad) {
+        const uint32_t qi = 4u * (uint32_t)__float_as_int(sb.x);
+        const float4 q0 = E.q[qi];
+        h.mi = (uint32_t)__float_as_int(q0.w);
+        h.n = v3(sa.x, sa.y, sa.z);                                              // q.normal
+        if (want_uv) {  // (alpha, beta) as quad_test formed them (hittables.go:181-183)
+            const float4 q1 = E.q[qi + 1], q2 = E.q[qi + 2], q3 = E.q[qi + 3];
+            const V3 php = sub(h.pt, v3(q0.x, q0.y, q0.z));
+            const V3 w = v3(q3.x, q3.y, q3.z);
+            h.u = dot(w, cross(php, v3(q2.x, q2.y, q2.z)));
+            h.v = dot(w, cross(v3(q1.x, q1.y, q1.z), php));
+        }
+    } else if (h.hit) {
+        h.mi = RTX_DEV_SPHERE_MATERIAL(__float_as_int(sb.w));
+        if (want_uv) {                                                           // hittables.go:122-126
+            const UV uv = sphere_uv(h.n.x, h.n.y, h.n.z);
+            h.u = uv.u;
+            h.v = uv.v;
+        }
+    }
+    h.front = dot(r.d, h.n) < 0.0f;                                              // hittables.go:23
+    if (!h.front) h.n = scale(h.n, -1.0f);                                       // :24-26
+    return h;
+}
+
+// QUADS: the scene holds quads.  FIXED: the scene in the workgroup's LDS copy, else read from HBM.  NOISE: the scene has
+// a Perlin texture.
+template <bool QUADS, bool FIXED, bool NOISE>
+__global__ __launch_bounds__(64 * DIRECT_WAVES) void direct_paths(DirectPathParams p) {
+    extern __shared__ float4 lds_entries[];
+    SceneRef E;
+    if constexpr (FIXED) {
+        // scene_ref_fixed: the walk addresses LDS directly, so the copy must start at 0
+        if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) float4*)lds_entries != 0u) __builtin_trap();
+        const uint32_t m = p.n_entries + 1, nq4 = 4 * p.n_quads;
+        for (uint32_t i = threadIdx.x; i < m; i += 64 * DIRECT_WAVES) {
+            lds_entries[i] = p.entries[i];
+            lds_entries[LDS_B / 16 + i] = p.entries[m + i];
+        }
+        for (uint32_t i = threadIdx.x; i < nq4; i += 64 * DIRECT_WAVES) lds_entries[LDS_B / 16 + m + i] = p.entries[2 * m + i];
+        __syncthreads();
+        E = scene_ref_fixed(lds_entries, p.n_entries, p.n_quads, 0u, 0u);
+        E.prim_end = p.prim_end;
+    } else {
+        E = scene_ref(p.entries, p.n_entries, nullptr);
+    }
+    const uint32_t end = 16 * p.n_entries;  // the sentinel's position
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t twl = p.tile_w_log2, tw = 1u << twl, th = 64u >> twl;
+    const uint32_t tiles_x = tiles_x_of(p.width, twl);
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * DIRECT_WAVES + (threadIdx.x >> 6));
+    if (wave >= tiles_x * tiles_y_of(p.rows, twl)) return;  // (the whole wave)
+    const uint32_t tile_y = wave / tiles_x, tile_x = wave - tile_y * tiles_x;
+    const uint32_t px = tile_x * tw + (lane & (tw - 1u)), py = tile_y * th + (lane >> twl);
+    const bool live = px < p.width && py < p.rows;  // (a lane outside a ragged tile computes on the nearest pixel)
+    const uint32_t xx = px < p.width ? px : p.width - 1u, lr = py < p.rows ? py : p.rows - 1u;
+    const uint32_t x = p.x0 + xx, y = p.y0 + region_row(lr, p.rank, p.world, p.stripe_log2);
+    const uint32_t pixel = y * p.cam.image_width + x;  // the GLOBAL pixel index: the RNG's counter word
+    const V3 base = pixel_base(p.cam, x, y);
+    const uint32_t s0 = (uint32_t)p.seed, s1 = (uint32_t)(p.seed >> 32);
+    const LightTables tabs{p.materials, p.textures, p.texels, p.lights, p.n_lights};
+    const V3 bg = v3(p.cam.background[0], p.cam.background[1], p.cam.background[2]);
+    const V3 zero = v3(0.0f, 0.0f, 0.0f), one = v3(1.0f, 1.0f, 1.0f);
+    const uint32_t depth = p.cam.max_depth;
+    const bool want_uv = p.want_uv != 0u;
+
+    uint32_t k = p.k0;                  // the lane's sample
+    const uint32_t kend = p.k0 + p.kn;  // (at most 2^32 - 1: the entry's check)
+    uint32_t seg = 0, cam_draws = 0;
+    bool shadow = false, diffuse = false;
+    V3 T = one, Lc = zero, pending = zero, bounce = zero;  // pending: T * radiance of the walking shadow ray; bounce: the saved direction
+    // the lane's slot of the tile-major moments: the pass continues the sums in k order (passes of one accumulator
+    // are ordered by the caller), so they are read here and written back at the end
+    const size_t slot = ((size_t)wave * 64u + lane) * 3u;
+    V3 S = zero, Q = zero;
+    if (live) {
+        S = v3(p.acc_s[slot], p.acc_s[slot + 1], p.acc_s[slot + 2]);
+        Q = v3(p.acc_q[slot], p.acc_q[slot + 1], p.acc_q[slot + 2]);
+    }
+    Ray r;
+    {
+        const PathRng rng{s0, s1, pixel, k};
+        r = camera_ray<false>(p.cam, base, rng, rng.block(0, 0), cam_draws);
+    }
+    Trav t{};
+    trav_begin(t, r, p.start);
+    Counters cnt{0, 0, 0, 0, 0, 0, 0};
+
+    for (;;) {
+        const bool parked = t.i >= end;
+        const bool pend = parked && k < kend;  // a finished walk, not folded yet
+        const uint32_t np = (uint32_t)__popcll(ballot(pend));
+        if (np >= p.refill || ballot(!parked) == 0) {
+            if (np == 0u) break;  // every lane parked and out of samples
+            // -- the fold step, whole wave.  What follows is computed by every lane on its own walk and kept where
+            //    `seg_end` (a parked closest walk) or `sh_end` (a parked shadow walk) says so.
+            const bool seg_end = pend && !shadow, sh_end = pend && shadow;
+            const PathHit h = path_hit<QUADS>(E, t, r, want_uv);
+            const bool hit = seg_end && h.hit && h.mi < p.n_materials;
+            const float4* mp = reinterpret_cast<const float4*>(p.materials + (hit ? h.mi : 0u));
+            const float4 m0 = mp[0], m1 = mp[1];
+            const uint32_t type = hit ? __float_as_uint(m0.x) : 0xFFFFFFFFu, tex = __float_as_uint(m0.y);
+            const float fuzz = m0.z, ior = m0.w;
+            const V3 albedo = v3(m1.x, m1.y, m1.z);
+            const PathRng rng{s0, s1, pixel, k};
+            const uint32_t e = seg + 1u;    // the scatter after segment seg
+            const U4 b0 = rng.block(e, 0);  // lockstep
+            const V3 ud = unit(r.d);                                    // materials.go:61, 96
+            const V3 mirror = reflect(ud, h.n);                         // materials.go:62, 108
+            // shade_hits' material section (rtx_shade.hip)
+            V3 colour = albedo;
+            if ((type == RTX_MAT_LAMBERTIAN || type == RTX_MAT_DIFFUSE_LIGHT) && tex != RTX_DEV_TEX_INLINE)
+                colour = texture_value<false, NOISE>(p.textures, p.texels, tex, h.u, h.v, h.pt, cnt);
+            uint32_t draws = 0;
+            bool scattered = false, emits = false;
+            V3 att = zero, em = zero, dir = zero;
+            if (type == RTX_MAT_LAMBERTIAN || type == RTX_MAT_METAL) {
+                const V3 s = rand_unit_on_sphere(rng, e, b0, draws);    // the per-lane rejection loop
+                if (type == RTX_MAT_LAMBERTIAN) {                       // materials.go:33-42
+                    dir = add(h.n, s);
+                    if (near_zero(dir)) dir = h.n;
+                    att = colour;
+                    scattered = true;
+                } else {                                                // materials.go:60-75
+                    const V3 sc = add(mirror, scale(s, fuzz));
+                    if (dot(sc, h.n) > 0.0f) {                          // else absorbed
+                        dir = sc;
+                        att = albedo;
+                        scattered = true;
+                    }
+                }
+            } else if (type == RTX_MAT_DIELECTRIC) {                    // materials.go:91-113
+                const float eta = h.front ? albedo.x : ior;
+                const float d = dot(scale(ud, -1.0f), h.n);
+                const float cos_t = d < 1.0f ? d : (d != d ? d : 1.0f); // float32(math.Min(float64(d), 1))
+                const float sin_t = (float)__builtin_sqrt(1.0 - (double)(cos_t * cos_t));
+                bool refl = sin_t * eta > 1.0f;
+                if (!refl) {                                            // short-circuit: draw only here
+                    const float r0 = h.front ? albedo.y : albedo.z;     // materials.go:116-118
+                    const float rf = r0 + (1.0f - r0) * (float)go_pow5(1.0 - (double)cos_t);
+                    refl = rf > unit_f32(b0.x);
+                }
+                dir = refl ? mirror : refract(ud, h.n, eta);
+                att = one;
+                scattered = true;
+            } else if (type == RTX_MAT_DIFFUSE_LIGHT) {                 // emits, never scatters
+                em = colour;
+                emits = true;
+            }
+            // the light sample at this hit (its own event range, lockstep block 0)
+            const uint32_t le = DIRECT_EVENT | e;
+            const U4 lb0 = rng.block(le, 0);
+            const bool lam = hit && type == RTX_MAT_LAMBERTIAN;  // (a Lambertian always scatters)
+            const bool want_light = lam && seg + 1u < depth && p.n_lights != 0u;
+            const LightSample ls = light_sample<NOISE>(tabs, want_light, m0, m1, h.pt, h.n, h.u, h.v, rng, le, lb0);
+
+            // -- the estimator, per lane; every * and + rounded on its own
+            bool sample_done = false, start_shadow = false, start_bounce = false;
+            V3 next_o = r.o, next_d = r.d;
+            if (sh_end) {
+                if (t.hit < 0) Lc = add(Lc, pending);
+                next_d = bounce;  // (the shadow ray started at the hit point: the origin stays)
+                shadow = false;
+                start_bounce = true;
+            } else if (seg_end) {
+                if (seg >= depth) {  // (max_depth 0: GetColor returns black before it looks, ray.go:33)
+                    sample_done = true;
+                } else if (!hit) {
+                    Lc = add(Lc, mul(T, bg));                           // ray.go:52
+                    sample_done = true;
+                } else {
+                    if (emits && !diffuse) Lc = add(Lc, mul(T, em));    // ray.go:41, 47
+                    if (ls.sampled) pending = mul(T, ls.rad);
+                    if (!scattered) {
+                        sample_done = true;
+                    } else {
+                        T = mul(T, att);                                // ray.go:47-50
+                        diffuse = lam && p.n_lights != 0u;
+                        ++seg;
+                        if (seg >= depth) {
+                            sample_done = true;                         // the depth cap: nothing more is added
+                        } else if (ls.sampled) {
+                            bounce = dir;
+                            next_o = h.pt;
+                            next_d = ls.w;
+                            shadow = true;
+                            start_shadow = true;
+                        } else {
+                            next_o = h.pt;
+                            next_d = dir;
+                            start_bounce = true;
+                        }
+                    }
+                }
+            }
+            if (sample_done) {  // S += c; Q += c * c, in k order (a lane's samples follow one another)
+                S = add(S, Lc);
+                Q = v3(Q.x + __fmul_rn(Lc.x, Lc.x), Q.y + __fmul_rn(Lc.y, Lc.y), Q.z + __fmul_rn(Lc.z, Lc.z));
+                ++k;
+                T = one;
+                Lc = zero;
+                seg = 0;
+                diffuse = false;
+            }
+            // the next sample's camera ray (the whole wave: its rejection loop and unit's votes)
+            const PathRng crng{s0, s1, pixel, k};
+            const Ray cr = camera_ray<false>(p.cam, base, crng, crng.block(0, 0), cam_draws);
+            Ray nr = Ray{next_o, next_d};
+            if (sample_done) nr = cr;
+            const bool go = start_shadow || start_bounce || (sample_done && k < kend);
+            Trav nt;
+            trav_begin(nt, nr, go ? p.start : end);  // (whole wave: its votes)
+            if (start_shadow) nt.closest = 0.999f;   // the shadow ray's tmax; tmin = 0.001 either way
+            if (pend) {
+                r = nr;
+                t = nt;  // (out of samples: parked on the sentinel for good)
+            }
+        }
+        // DIRECT_STEPS walk steps: the med3 / div_by forms when every walking lane's ray is safe (traverse_phase)
+        uint32_t idle = 0;
+        if (ballot(!t.safe && t.i < end) == 0) {
+#pragma unroll
+            for (uint32_t s = 0; s < DIRECT_STEPS; ++s) {
+                trav_step_batched<false, QUADS, FIXED, false, true>(t, r, E, cnt, end, p.prim_batch, idle);
+                if (shadow && t.hit >= 0) t.i = end;  // any-hit: park at the first accepted primitive
+            }
+        } else {
+#pragma unroll
+            for (uint32_t s = 0; s < DIRECT_STEPS; ++s) {
+                trav_step_batched<false, QUADS, FIXED, false, false>(t, r, E, cnt, end, p.prim_batch, idle);
+                if (shadow && t.hit >= 0) t.i = end;
+            }
+        }
+    }
+    if (live) {  // (a lane outside a ragged tile leaves its slot zero, as accumulate_samples does)
+        p.acc_s[slot] = S.x;
+        p.acc_s[slot + 1] = S.y;
+        p.acc_s[slot + 2] = S.z;
+        p.acc_q[slot] = Q.x;
+        p.acc_q[slot + 1] = Q.y;
+        p.acc_q[slot + 2] = Q.z;
+    }
+}
+
+template <bool QUADS, bool FIXED>
+hipError_t launch_paths_noise(const DirectPathParams& p, bool noise, hipStream_t stream) {
+    const size_t shmem = FIXED ? LDS_B + (p.n_entries + 1) * 16 + p.n_quads * 64 : 0;  // trace_lds_bytes (rtx_trace.hip)
+    const uint64_t tiles = (uint64_t)tiles_x_of(p.width, p.tile_w_log2) * tiles_y_of(p.rows, p.tile_w_log2);
+    const dim3 grid((uint32_t)((tiles + DIRECT_WAVES - 1) / DIRECT_WAVES)), block(64 * DIRECT_WAVES);
+    if (noise) hipLaunchKernelGGL((direct_paths<QUADS, FIXED, true>), grid, block, shmem, stream, p);
+    else hipLaunchKernelGGL((direct_paths<QUADS, FIXED, false>), grid, block, shmem, stream, p);
+    return hipGetLastError();
+}
+
+template <bool COUNT, bool QUADS, bool FIXED>
+hipError_t launch_noise(const DirectParams& p, bool noise, hipStream_t stream) {
+    const size_t shmem = FIXED ? LDS_B + (p.n_entries + 1) * 16 + p.n_quads * 64 : 0;  // trace_lds_bytes (rtx_trace.hip)
+    const uint64_t waves = ((uint64_t)p.n + p.range - 1) / p.range;
+    const dim3 grid((uint32_t)((waves + DIRECT_WAVES - 1) / DIRECT_WAVES)), block(64 * DIRECT_WAVES);
+    if (noise) hipLaunchKernelGGL((direct_lights<COUNT, QUADS, FIXED, true>), grid, block, shmem, stream, p);
+    else hipLaunchKernelGGL((direct_lights<COUNT, QUADS, FIXED, false>), grid, block, shmem, stream, p);
+    return hipGetLastError();
+}
+
+template <bool COUNT>
+hipError_t launch_count(const DirectParams& p, bool noise, hipStream_t stream) {
+    const bool fixed = trace_placement(p.n_entries, p.n_quads) == RTX_SCENE_IN_LDS;
+    if (p.n_quads) return fixed ? launch_noise<COUNT, true, true>(p, noise, stream) : launch_noise<COUNT, true, false>(p, noise, stream);
+    return fixed ? launch_noise<COUNT, false, true>(p, noise, stream) : launch_noise<COUNT, false, false>(p, noise, stream);
+}
+
+}  // namespace
+
+hipError_t launch_direct(const DirectParams& p, bool count, bool noise, hipStream_t stream) {
+    if (p.n == 0) return hipSuccess;
+    if (p.n > DIRECT_LAUNCH_MAX || p.range == 0 || p.range % 64u != 0 || !p.hits || !p.keys || !p.out || !p.entries ||
+        !p.materials || !p.textures || !p.texels || (p.n_lights && !p.lights) || p.n_lights > (1u << 24) ||
+        (count && !p.counters))
+        return hipErrorInvalidValue;
+    return count ? launch_count<true>(p, noise, stream) : launch_count<false>(p, noise, stream);
+}
+
+hipError_t launch_direct_paths(const DirectPathParams& p, bool noise, hipStream_t stream) {
+    const uint64_t P = (uint64_t)p.width * p.rows;
+    if (P == 0 || p.kn == 0) return hipSuccess;
+    if (P > 0xFFFFFFFFull || (uint64_t)p.k0 + p.kn > 0xFFFFFFFFull || p.tile_w_log2 > 6u || p.refill == 0 || p.refill > 64u ||
+        p.world == 0 || p.rank >= p.world || !p.entries || !p.materials || !p.textures || !p.texels || !p.acc_s || !p.acc_q ||
+        (p.n_lights && !p.lights) || p.n_lights > (1u << 24))
+        return hipErrorInvalidValue;
+    const bool fixed = trace_placement(p.n_entries, p.n_quads) == RTX_SCENE_IN_LDS;
+    if (p.n_quads) return fixed ? launch_paths_noise<true, true>(p, noise, stream) : launch_paths_noise<true, false>(p, noise, stream);
+    return fixed ? launch_paths_noise<false, true>(p, noise, stream) : launch_paths_noise<false, false>(p, noise, stream);
+}
+
+}  // namespace rtxd

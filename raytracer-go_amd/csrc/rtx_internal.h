@@ -8,7 +8,8 @@
 //   rtx_bands.hip      rtx_render(_ex): the bands and their assembly
 //   rtx_accum.hip      progressive passes and their previews; rtx_trace_capi.hip: ray queries; rtx_shade_capi.hip:
 //                      camera rays and material scatter for a batch; rtx_guides_capi.hip: guide images and the
-//                      preview filter; rtx_capi.hip: scene create / destroy
+//                      preview filter; rtx_direct_capi.hip: light samples and shadow rays for a batch;
+//                      rtx_capi.hip: scene create / destroy
 //
 // A unit that defines RTX_HOST_ONLY before including this header sees the first half only, which names no HIP type:
 // it compiles with the plain host compiler and links without the runtime (tests/test_pack_layout.py).
@@ -54,6 +55,11 @@ struct rtx_scene {
     std::map<int, std::unique_ptr<rtxh::DeviceCopy>> copies;
     bool has_image = false;  // some texture is an ImageTexture: hits need UV
     bool has_noise = false;  // some texture is a Perlin NoiseTexture
+    // Direct light sampling: the emitter table, built from `base` by the first call that asks for it
+    // (build_lights, mu held) and never by scene creation.  lighttab: 16 floats per emitter, the device records.
+    bool lights_built = false;
+    std::vector<rtx_light> lights;
+    std::vector<float> lighttab;
     std::mutex mu;
 };
 
@@ -79,6 +85,13 @@ int check_camera(const rtx_camera* cam);
 int check_region(const rtx_camera* cam, const rtx_region* r);
 uint32_t region_rows(const rtx_region* r);
 uint32_t band_stripe(int n);
+// The emitter table of a scene's entries in the reference walk's order (`base`), its quad table and its materials
+// (rtx.h, "direct light sampling"): `lights` in table order and, when tab != nullptr, 16 floats per emitter for the
+// device: (centre | Q, radius | 0), (u, area), (v, kind: RTX_PRIM_*), (the quad's normal, material).
+int build_lights(const std::vector<rtx_entry>& base, const std::vector<float>& quadtab,
+                 const std::vector<rtx_material>& materials, std::vector<rtx_light>& lights, std::vector<float>* tab);
+// The scene's own table, built on first use (s->mu held).
+int scene_lights(rtx_scene* s);
 
 // A walk in device form (rtx_layout.h): what upload_layout copies to the device and what a render needs to know
 // of it.
@@ -142,6 +155,11 @@ struct DeviceCopy {
     // Path building blocks (rtx_shade_device): counters and events of their own (first shade).
     DeviceBuffer shade_counters;
     hipEvent_t sev0 = nullptr, sev1 = nullptr;
+    // Direct light sampling (rtx_direct_device): the emitter records, counters and events of their
+    // own (first call).
+    DeviceBuffer lights;
+    DeviceBuffer direct_counters;
+    hipEvent_t dev0 = nullptr, dev1 = nullptr;
 
     unsigned long long* slot(uint32_t k) const { return counters.as<unsigned long long>() + k; }
     // a counter slot's low word, for the three the kernels claim from
@@ -235,6 +253,11 @@ int ensure_trace(rtx_scene* s, DeviceCopy* c, uint32_t oct, const DeviceLayout**
 // rtx_guides_device after its checks, with s->mu held (rtx_accum_preview*).
 int guides_locked(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const rtx_region* region, uint32_t first_sample,
                   uint32_t count, rtx_guide* d_guides, hipStream_t stream, rtx_guide_stats* stats);
+
+// ---- rtx_direct_capi.hip -------------------------------------------------------------------------------------
+// One fused direct-light pass into an accumulator's moments (rtx_accum_add_direct after its checks), s->mu held.
+int direct_pass_locked(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const rtx_region* region, uint32_t tile_w_log2,
+                       uint32_t first, uint32_t count, float* acc_s, float* acc_q, hipStream_t stream, rtx_stats* stats);
 
 // ---- rtx_bands.hip -------------------------------------------------------------------------------------------
 int render_bands_locked(rtx_scene* s, const rtx_camera* cam, uint64_t seed, int n_gpus, uint32_t flags, float* out_rgb,

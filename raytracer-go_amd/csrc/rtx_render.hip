@@ -70,10 +70,10 @@ void free_copy(DeviceCopy& c) {
     (void)hipDeviceSynchronize();  // no render of this copy still running
     for (DeviceLayout& l : c.lay) l.entries.release();
     for (DeviceLayout& l : c.trace_lay) l.entries.release();
-    for (DeviceBuffer* b : {&c.rank_sphere, &c.trace_counters, &c.shade_counters, &c.materials, &c.textures, &c.texels,
-                            &c.counters})
+    for (DeviceBuffer* b : {&c.rank_sphere, &c.trace_counters, &c.shade_counters, &c.lights, &c.direct_counters, &c.materials,
+                            &c.textures, &c.texels, &c.counters})
         b->release();
-    for (hipEvent_t ev : {c.sev0, c.sev1, c.tev0, c.tev1, c.ev0, c.ev1})
+    for (hipEvent_t ev : {c.dev0, c.dev1, c.sev0, c.sev1, c.tev0, c.tev1, c.ev0, c.ev1})
         if (ev) (void)hipEventDestroy(ev);
 }
 

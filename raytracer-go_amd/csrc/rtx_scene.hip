@@ -222,6 +222,83 @@ void quad_table(const rtx_scene_desc* d, std::vector<float>& tab) {
     }
 }
 
+// The emitter table (rtx.h, "direct light sampling"): the spheres, then the quads, that the walk's
+// entries name and whose material is a DiffuseLight, each once, in table order.  Every float operation is float32 and
+// rounded on its own (the unit is built without contraction): area = (4 * PiF32) * (r * r), or Len(Cross(u, v)).
+int build_lights(const std::vector<rtx_entry>& base, const std::vector<float>& quadtab,
+                 const std::vector<rtx_material>& materials, std::vector<rtx_light>& lights, std::vector<float>* tab) {
+    struct Emitter {
+        uint32_t index, material;
+        float a[4], u[3], v[3], n[3];  // a: (centre, radius) or (Q, 0)
+    };
+    std::vector<Emitter> sph, quad;
+    for (const rtx_entry& e : base) {
+        int32_t tag;
+        std::memcpy(&tag, &e.b[3], 4);
+        if (tag == RTX_E_NODE) continue;
+        Emitter m{};
+        if (tag == RTX_E_QUAD) {
+            std::memcpy(&m.index, &e.b[0], 4);
+            const float* q = &quadtab[(size_t)m.index * 16];
+            std::memcpy(&m.material, q + 3, 4);
+            std::memcpy(m.a, q, 12);
+            std::memcpy(m.u, q + 4, 12);
+            std::memcpy(m.v, q + 8, 12);
+            std::memcpy(m.n, e.a, 12);
+        } else {
+            std::memcpy(&m.index, &e.b[1], 4);
+            m.material = (uint32_t)tag;
+            std::memcpy(m.a, e.a, 16);
+        }
+        if (m.material >= materials.size() || materials[m.material].type != RTX_MAT_DIFFUSE_LIGHT) continue;
+        (tag == RTX_E_QUAD ? quad : sph).push_back(m);
+    }
+    const auto by_index = [](const Emitter& x, const Emitter& y) { return x.index < y.index; };
+    const auto same = [](const Emitter& x, const Emitter& y) { return x.index == y.index; };
+    for (std::vector<Emitter>* v : {&sph, &quad}) {
+        std::stable_sort(v->begin(), v->end(), by_index);
+        v->erase(std::unique(v->begin(), v->end(), same), v->end());
+    }
+    lights.clear();
+    if (tab) tab->clear();
+    const auto put = [&](const Emitter& m, uint32_t kind, float area) {
+        if (!(std::isfinite(area) && area > 0.0f)) return;
+        lights.push_back(rtx_light{(kind << 28) | m.index, area});
+        if (!tab) return;
+        float rec[16] = {m.a[0], m.a[1], m.a[2], m.a[3], m.u[0], m.u[1], m.u[2], area,
+                         m.v[0], m.v[1], m.v[2], 0.0f,   m.n[0], m.n[1], m.n[2], 0.0f};
+        std::memcpy(&rec[11], &kind, 4);
+        std::memcpy(&rec[15], &m.material, 4);
+        tab->insert(tab->end(), rec, rec + 16);
+    };
+    const float pi32 = 3.14159274101257324f;  // PiF32, math.go:48
+    for (const Emitter& m : sph) {
+        const float r = m.a[3];
+        if (!(r > 0.0f)) continue;
+        put(m, RTX_PRIM_SPHERE, (4.0f * pi32) * (r * r));
+    }
+    for (const Emitter& m : quad) {
+        const float cx = m.u[1] * m.v[2] - m.u[2] * m.v[1], cy = m.u[2] * m.v[0] - m.u[0] * m.v[2],
+                    cz = m.u[0] * m.v[1] - m.u[1] * m.v[0];  // vec3.go:129-135
+        const float lsq = cx * cx + cy * cy + cz * cz;       // vec3.go:115-117
+        put(m, RTX_PRIM_QUAD, (float)std::sqrt((double)lsq));  // vec3.go:119-121
+    }
+    if (lights.size() > (1u << 24)) {
+        const size_t L = lights.size();
+        lights.clear();
+        if (tab) tab->clear();
+        return fail(RTX_ERR_INVALID_ARG, "%zu emitters: more than 2^24 (the light index is drawn from one float32)", L);
+    }
+    return RTX_OK;
+}
+
+int scene_lights(rtx_scene* s) {
+    if (s->lights_built) return RTX_OK;
+    if (int rc = build_lights(s->base, s->quadtab, s->materials, s->lights, &s->lighttab)) return rc;
+    s->lights_built = true;
+    return RTX_OK;
+}
+
 namespace {
 
 // The walk's tree (rtx_topology.h): 0 = the caller's, 1 = guarded, 2 = unguarded.  Default:
@@ -699,6 +776,40 @@ int rtx_walk_tree(const rtx_scene_desc* d, uint32_t flags, uint32_t octant, rtx_
     const bool has = d->n_roots == 1 &&
                      (near ? tier_topology(flags, ref, d, t) : (mode != 0 && rtxd::build_topology(ref, mode == 1, t)));
     return copy_tree(has ? &t : nullptr, octant, nodes, cap, n_nodes, root);
+}
+
+namespace {
+int copy_lights(const std::vector<rtx_light>& v, rtx_light* out, uint32_t cap, uint32_t* n) {
+    *n = (uint32_t)v.size();
+    if (out && cap >= v.size() && !v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(rtx_light));
+    return RTX_OK;
+}
+}  // namespace
+
+int rtx_lights(const rtx_scene_desc* d, rtx_light* out, uint32_t cap, uint32_t* n) {
+    g_last_error.clear();
+    if (!d || !n) return fail(RTX_ERR_INVALID_ARG, "bad argument");
+    *n = 0;
+    if (d->n_lists && !d->lists) return fail(RTX_ERR_INVALID_ARG, "lists is NULL");
+    if (d->n_list_refs && !d->list_refs) return fail(RTX_ERR_INVALID_ARG, "list_refs is NULL");
+    std::vector<rtx_entry> base;
+    if (int rc = flatten(d, base)) return rc;
+    std::vector<float> quadtab;
+    quad_table(d, quadtab);
+    std::vector<rtx_light> lights;
+    if (int rc = build_lights(base, quadtab, std::vector<rtx_material>(d->materials, d->materials + d->n_materials), lights, nullptr))
+        return rc;
+    return copy_lights(lights, out, cap, n);
+}
+
+int rtx_scene_lights(const rtx_scene* scene, rtx_light* out, uint32_t cap, uint32_t* n) {
+    g_last_error.clear();
+    if (!scene || !n) return fail(RTX_ERR_INVALID_ARG, "bad argument");
+    *n = 0;
+    rtx_scene* s = const_cast<rtx_scene*>(scene);  // (the table is made on first use, under the scene's mutex)
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (int rc = scene_lights(s)) return rc;
+    return copy_lights(s->lights, out, cap, n);
 }
 
 uint64_t rtx_scene_device_bytes(const rtx_scene* s) {

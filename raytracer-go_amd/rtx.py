@@ -47,6 +47,9 @@ RTX_TRACE_COUNTERS = 4  # the counting instantiation (with stats)
 RTX_BOUNCE_SCATTERED = 1  # Bounce.flags: Scatter returned true; attenuation and ray are ScatterInfo's
 RTX_BOUNCE_EMITS = 2  # Bounce.flags: the material is a DiffuseLight; emitted is its texture
 RTX_SHADE_COUNTERS = 1  # the counting instantiation (with stats)
+RTX_DIRECT_SAMPLED = 1  # DirectSample.flags: a light point was sampled; radiance, ray and geom are its
+RTX_DIRECT_VISIBLE = 2  # DirectSample.flags: the shadow ray met no primitive
+RTX_DIRECT_COUNTERS = 1  # the counting instantiation (with stats)
 
 
 def RTX_TRACE_OCTANT(o: int) -> int:
@@ -167,6 +170,23 @@ class ShadeStats(ctypes.Structure):  # rtx_shade_stats
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class Light(ctypes.Structure):  # rtx_light, 8 B
+    _fields_ = [("prim", c_uint32), ("area", c_float)]
+
+
+class DirectSample(ctypes.Structure):  # rtx_direct_sample, 64 B
+    _fields_ = [("radiance", c_float * 3), ("flags", c_uint32), ("ray", TraceRay), ("light", c_uint32),
+                ("rng_draws", c_uint32), ("geom", c_float), ("reserved", c_uint32)]
+
+
+class DirectStats(ctypes.Structure):  # rtx_direct_stats
+    _fields_ = [("n", c_uint64), ("sampled", c_uint64), ("visible", c_uint64), ("rng_draws", c_uint64),
+                ("kernel_ms", c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class Guide(ctypes.Structure):  # rtx_guide, 32 B
     _fields_ = [("albedo", c_float * 3), ("cover", c_float), ("normal", c_float * 3), ("depth", c_float)]
 
@@ -197,12 +217,20 @@ class DenoiseParams(ctypes.Structure):  # rtx_denoise_params; DenoiseParams.defa
 
 
 def __getattr__(name: str):
-    """RAY_DTYPE / HIT_DTYPE / KEY_DTYPE / BOUNCE_DTYPE / GUIDE_DTYPE: the numpy structured dtypes of rtx_ray, rtx_hit,
-    rtx_path_key, rtx_bounce and rtx_guide (numpy is imported on first use, as everywhere in this module)."""
+    """RAY_DTYPE / HIT_DTYPE / KEY_DTYPE / BOUNCE_DTYPE / GUIDE_DTYPE / LIGHT_DTYPE / DIRECT_DTYPE: the numpy structured
+    dtypes of rtx_ray, rtx_hit, rtx_path_key, rtx_bounce, rtx_guide, rtx_light and rtx_direct_sample (numpy is imported on
+    first use, as everywhere in this module)."""
     if name == "GUIDE_DTYPE":
         import numpy as np
         globals().update(GUIDE_DTYPE=np.dtype([("albedo", "<f4", (3,)), ("cover", "<f4"), ("normal", "<f4", (3,)),
                                                ("depth", "<f4")]))
+        return globals()[name]
+    if name in ("LIGHT_DTYPE", "DIRECT_DTYPE"):
+        import numpy as np
+        ray = __getattr__("RAY_DTYPE")
+        globals().update(LIGHT_DTYPE=np.dtype([("prim", "<u4"), ("area", "<f4")]),
+                         DIRECT_DTYPE=np.dtype([("radiance", "<f4", (3,)), ("flags", "<u4"), ("ray", ray), ("light", "<u4"),
+                                                ("rng_draws", "<u4"), ("geom", "<f4"), ("reserved", "<u4")]))
         return globals()[name]
     if name in ("RAY_DTYPE", "HIT_DTYPE", "KEY_DTYPE", "BOUNCE_DTYPE"):
         import numpy as np
@@ -237,6 +265,8 @@ RTX_SYMBOLS = [
     "rtx_denoise", "rtx_accum_preview_device", "rtx_accum_preview", "rtx_accum_preview_ppm",
     # adaptive sampling (ABI 10, additive)
     "rtx_accum_add_adaptive", "rtx_accum_tile_shape", "rtx_accum_sample_counts_device", "rtx_accum_sample_counts",
+    # direct light sampling (ABI 10, additive)
+    "rtx_lights", "rtx_scene_lights", "rtx_direct_device", "rtx_direct", "rtx_accum_add_direct",
 ]
 RTXHOST_SYMBOLS = [
     "rtxhost_build_scene", "rtxhost_scene_free", "rtxhost_scene_desc", "rtxhost_scene_camera",
@@ -399,6 +429,18 @@ def load() -> ctypes.CDLL:
         L.rtx_accum_sample_counts_device.restype = c_int
         L.rtx_accum_sample_counts.argtypes = [c_void_p, c_void_p]
         L.rtx_accum_sample_counts.restype = c_int
+    if hasattr(L, "rtx_direct_device"):  # direct light sampling (ABI 10, additive)
+        L.rtx_lights.argtypes = [POINTER(SceneDesc), c_void_p, c_uint32, POINTER(c_uint32)]
+        L.rtx_lights.restype = c_int
+        L.rtx_scene_lights.argtypes = [c_void_p, c_void_p, c_uint32, POINTER(c_uint32)]
+        L.rtx_scene_lights.restype = c_int
+        L.rtx_direct_device.argtypes = [c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p,
+                                        POINTER(DirectStats)]
+        L.rtx_direct_device.restype = c_int
+        L.rtx_direct.argtypes = [c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(DirectStats)]
+        L.rtx_direct.restype = c_int
+        L.rtx_accum_add_direct.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, POINTER(Stats)]
+        L.rtx_accum_add_direct.restype = c_int
     _lib = L
     return L
 
@@ -735,6 +777,46 @@ class DeviceScene:
         out = out.reshape(rows, region.width)
         return (out, st) if stats else out
 
+    def lights(self):
+        """rtx_scene_lights: the scene's emitter table, an array of LIGHT_DTYPE (prim coded as Hit.prim, area)."""
+        L = load()
+        return _light_table(lambda out, cap, n: L.rtx_scene_lights(self._h, out, cap, n), "rtx_scene_lights")
+
+    def direct_device(self, seed: int, hits_ptr: int, keys_ptr: int, n: int, out_ptr: int, flags: int = 0, stream: int = 0,
+                      stats: bool = False):
+        """rtx_direct_device: n records of rtx_hit / rtx_path_key in lock step -> n rtx_direct_sample at out_ptr,
+        device memory of the current device (16-B aligned).  Enqueues and returns None, or with stats=True waits and
+        returns the DirectStats (flags | RTX_DIRECT_COUNTERS fills its counters)."""
+        st = DirectStats() if stats else None
+        check(load().rtx_direct_device(self._h, seed, c_void_p(hits_ptr), c_void_p(keys_ptr), n, c_void_p(out_ptr), flags,
+                                       c_void_p(stream), ctypes.byref(st) if st is not None else None), "rtx_direct_device")
+        return st
+
+    def direct(self, hits, keys, seed: int, stats: bool = False, flags: int = 0):
+        """rtx_direct: numpy arrays of HIT_DTYPE and KEY_DTYPE of one shape in, an array of DIRECT_DTYPE of that shape
+        out (and the DirectStats with stats=True, counters filled with flags=RTX_DIRECT_COUNTERS).  Blocking."""
+        import numpy as np
+        types = [__getattr__(t) for t in ("HIT_DTYPE", "KEY_DTYPE")]
+        arrs = [np.asarray(a) for a in (hits, keys)]
+        for a, t, what in zip(arrs, types, ("hits", "keys")):
+            if a.dtype != t:
+                raise TypeError(f"{what} must have dtype {t}, not {a.dtype}")
+            if a.shape != arrs[0].shape:
+                raise ValueError("hits and keys must have one shape")
+        n = arrs[0].size
+        src = []
+        for a, t in zip(arrs, types):  # 16-B aligned copies
+            b = _aligned_empty(n, t)
+            b[...] = a.reshape(-1)
+            src.append(b)
+        out = _aligned_empty(n, __getattr__("DIRECT_DTYPE"))
+        st = DirectStats() if stats else None
+        check(load().rtx_direct(self._h, seed, *[b.ctypes.data_as(c_void_p) for b in src], n,
+                                out.ctypes.data_as(c_void_p), flags, ctypes.byref(st) if st is not None else None),
+              "rtx_direct")
+        out = out.reshape(arrs[0].shape)
+        return (out, st) if stats else out
+
     def accumulator(self, cam: Camera, seed: int, region: Region) -> "Accumulator":
         """rtx_accum_create on the current device: progressive passes over `region` (close it before the scene)."""
         return Accumulator(self, cam, seed, region)
@@ -770,6 +852,15 @@ class Accumulator:
         st = Stats() if (stats or counters) else None
         check(load().rtx_accum_add(self._h, count, c_void_p(stream), flags | (RTX_FLAG_COUNTERS if counters else 0),
                                    ctypes.byref(st) if st is not None else None), "rtx_accum_add")
+        return st
+
+    def add_direct(self, count: int, stream: int = 0, stats: bool = False, flags: int = 0):
+        """rtx_accum_add_direct: `count` more samples per pixel by the direct-light estimator, one fused
+        kernel.  An accumulator is plain, adaptive or direct until reset().  Returns the pass's Stats with stats=True
+        (which waits), else None."""
+        st = Stats() if stats else None
+        check(load().rtx_accum_add_direct(self._h, count, c_void_p(stream), flags,
+                                          ctypes.byref(st) if st is not None else None), "rtx_accum_add_direct")
         return st
 
     def add_adaptive(self, count: int, rel_tol: float, min_samples: int = 1, stream: int = 0, stats: bool = True,
@@ -884,6 +975,22 @@ def _aligned_empty(n: int, dtype):
     raw = np.empty(n * dtype.itemsize + 16, np.uint8)
     off = (-raw.ctypes.data) % 16
     return raw[off: off + n * dtype.itemsize].view(dtype)
+
+
+def _light_table(call, where: str):
+    import numpy as np
+    n = c_uint32()
+    check(call(None, 0, ctypes.byref(n)), where)
+    out = np.zeros(n.value, __getattr__("LIGHT_DTYPE"))
+    if n.value:
+        check(call(out.ctypes.data_as(c_void_p), n.value, ctypes.byref(n)), where)
+    return out
+
+
+def lights(desc_ptr):
+    """rtx_lights: the emitter table of a scene description, an array of LIGHT_DTYPE.  Host only: no scene, no device."""
+    L = load()
+    return _light_table(lambda out, cap, n: L.rtx_lights(desc_ptr, out, cap, n), "rtx_lights")
 
 
 def camera_rays_device(cam: Camera, seed: int, region: Region, first: int, count: int, rays_ptr: int, keys_ptr: int = 0,
