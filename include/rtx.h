@@ -449,7 +449,11 @@ uint32_t rtx_region_row(const rtx_region* region, uint32_t i);
  * in World.Add order; the k-th NewBVH call (pre-order) takes Intn(3) from word
  * bvh_draw0 + k of the global host stream of bvh_seed (the RNG contract, DESIGN.md
  * §3), which is the axis the host builder draws.  The scene equals the one
- * rtx_scene_create makes from the host-built tree (same entries, tests).  build_ms
+ * rtx_scene_create makes from NewBVHFromWorld's tree over this sphere table: the same
+ * entries byte for byte, a sphere entry's sphere word being the index into `spheres`
+ * (Add order), so rtx_hit.prim and rtx_light.prim name the caller's spheres
+ * (tests/test_bvh_gpu.py against tests/bvh_ref.py).  A tree built over a reordered
+ * copy of the table, as the host mirror's, differs in that word alone.  build_ms
  * (optional) receives the build's wall time.                                        */
 int rtx_scene_create_spheres(const rtx_sphere* spheres, uint32_t n_spheres, const rtx_material* materials,
                              uint32_t n_materials, const rtx_texture* textures, uint32_t n_textures,

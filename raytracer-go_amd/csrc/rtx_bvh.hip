@@ -148,13 +148,15 @@ __global__ void node_boxes(const DevNode* __restrict__ nodes, const uint32_t* __
     }
 }
 
-__device__ __forceinline__ void put_prim(rtx_entry* e, const rtx_sphere& s, uint32_t rank) {
+// A sphere's entry; `index` is its place in the caller's table (World.Add order), as rtx_scene_create's emit()
+// writes it: rtx_hit.prim and rtx_light.prim are read from that word.
+__device__ __forceinline__ void put_prim(rtx_entry* e, const rtx_sphere& s, uint32_t index) {
     e->a[0] = s.center[0];
     e->a[1] = s.center[1];
     e->a[2] = s.center[2];
     e->a[3] = s.radius;
     e->b[0] = s.radius * s.radius;  // hittables.go:100
-    e->b[1] = __int_as_float((int)rank);
+    e->b[1] = __int_as_float((int)index);
     e->b[2] = 0.0f;
     e->b[3] = __int_as_float((int)s.material);
 }
@@ -180,7 +182,8 @@ __global__ void emit_entries(const DevNode* __restrict__ nodes, uint32_t n_nodes
     if (nd.n <= 2) {
         for (uint32_t k = 0; k < nd.n; ++k) {
             rtx_entry p;
-            put_prim(&p, sp[perm[nd.off + k]], nd.off + k);
+            const uint32_t index = perm[nd.off + k];
+            put_prim(&p, sp[index], index);
             out[nd.entry + 1 + k] = p;
         }
     }
