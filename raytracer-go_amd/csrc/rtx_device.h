@@ -37,7 +37,9 @@ __device__ __forceinline__ V3 cross(V3 l, V3 r) {                               
 // field 2..252): one Newton step with fma on v_rcp_f32 (3 VALU), which equals the IEEE quotient
 // on all 4.2e9 such inputs (scripts/micro/fastrcp_check.hip, exhaustive on the GPU); else the
 // compiler's division (~10 VALU).  The vote is wave-uniform, so the branch does not diverge.
-__device__ __forceinline__ bool rcp_fast_ok(float x) { return ((__float_as_uint(x) >> 23) & 0xFFu) - 2u <= 250u; }
+// (rcp_exp_off: the exponent field less 2, so that the largest of several values' offsets decides for all of them)
+__device__ __forceinline__ uint32_t rcp_exp_off(float x) { return ((__float_as_uint(x) >> 23) & 0xFFu) - 2u; }
+__device__ __forceinline__ bool rcp_fast_ok(float x) { return rcp_exp_off(x) <= 250u; }
 __device__ __forceinline__ float rcp_newton(float x) {
     const float y0 = __builtin_amdgcn_rcpf(x);
     return __builtin_fmaf(__builtin_fmaf(-x, y0, 1.0f), y0, y0);
@@ -50,8 +52,7 @@ __device__ __forceinline__ float rcp_ieee(float x) {
 // whose fma residual changes sign.  The expansion's 2^32 pre-scaling is needed only below 2^-96,
 // so it runs (the builtin) only when a lane of the wave has 0 <= x < 2^-96; its +-0 / +inf
 // pass-through is left out: v_sqrt returns those exactly and both residuals then keep them.
-__device__ __forceinline__ float sqrt_rn(float x) {
-    if (__builtin_amdgcn_ballot_w64(x < 0x1p-96f && x >= 0.0f) != 0) return __builtin_sqrtf(x);
+__device__ __forceinline__ float sqrt_rn_fast(float x) {  // x >= 2^-96 (a negative or NaN x: NaN)
     float s = __builtin_amdgcn_sqrtf(x);
     const float sp = __uint_as_float(__float_as_uint(s) - 1u), sn = __uint_as_float(__float_as_uint(s) + 1u);
     const float rp = __builtin_fmaf(-sp, s, x), rn = __builtin_fmaf(-sn, s, x);
@@ -59,9 +60,21 @@ __device__ __forceinline__ float sqrt_rn(float x) {
     if (rn > 0.0f) s = sn;
     return s;
 }
-__device__ __forceinline__ V3 unit(V3 v) {                                                         // vec3.go:103-113
-    float l = sqrt_rn(lensq(v));
-    return scale(v, rcp_ieee(l));
+__device__ __forceinline__ float sqrt_rn(float x) {
+    if (__builtin_amdgcn_ballot_w64(x < 0x1p-96f && x >= 0.0f) != 0) return __builtin_sqrtf(x);
+    return sqrt_rn_fast(x);
+}
+// Unit (vec3.go:103-113): v * (1 / sqrt(lensq(v))), both correctly rounded.  One vote on q = lensq(v) decides both
+// fast forms: when every active lane's q lies in [2^-96, inf) — one unsigned compare on its bits, which a negative
+// or NaN q fails —, sqrt_rn_fast applies and l = sqrt(q) lies in [2^-48, 2^64), inside rcp_newton's domain, so
+// rcp_ieee's vote is implied.  Else the compiler's sqrt and division for the whole wave: the fast forms equal them
+// wherever they apply, so a lane's bits do not depend on the side its wave took.  (Two votes, sqrt_rn's and
+// rcp_ieee's, each with its compares and branch, cost the headline step 0.55 ms: DESIGN.md §38.)
+__device__ __forceinline__ V3 unit(V3 v) {
+    const float q = lensq(v);
+    const bool fast = __float_as_uint(q) - 0x0F800000u < 0x7F800000u - 0x0F800000u;
+    if (__builtin_amdgcn_ballot_w64(!fast) == 0) return scale(v, rcp_newton(sqrt_rn_fast(q)));
+    return scale(v, 1.0f / __builtin_sqrtf(q));
 }
 __device__ __forceinline__ bool near_zero(V3 v) {                                                  // vec3.go:170-172
     return __builtin_fabsf(v.x) < 1e-8f && __builtin_fabsf(v.y) < 1e-8f && __builtin_fabsf(v.z) < 1e-8f;
@@ -863,32 +876,46 @@ struct Trav {
 // |1/d| <= 2^64 per axis and an origin within 2^32 (the near tree's boxes lie within 2^32, topology).
 // Rays outside these bounds take the reference's form, ray by ray (oracle.c restates the rule).
 __device__ __forceinline__ bool near_fma_ok(const Ray& r, const Trav& t) {
-    return __builtin_fabsf(t.ix) <= 0x1p64f && __builtin_fabsf(t.iy) <= 0x1p64f && __builtin_fabsf(t.iz) <= 0x1p64f &&
-           __builtin_fabsf(r.o.x) <= 0x1p32f && __builtin_fabsf(r.o.y) <= 0x1p32f && __builtin_fabsf(r.o.z) <= 0x1p32f;
+    return (__builtin_fabsf(t.ix) <= 0x1p64f) & (__builtin_fabsf(t.iy) <= 0x1p64f) & (__builtin_fabsf(t.iz) <= 0x1p64f) &
+           (__builtin_fabsf(r.o.x) <= 0x1p32f) & (__builtin_fabsf(r.o.y) <= 0x1p32f) & (__builtin_fabsf(r.o.z) <= 0x1p32f);
 }
 
 // FMA (the near pass): a ray is `safe` for the walk's fast forms only when the FMA form applies too.
 template <bool FMA = false>
 __device__ __forceinline__ void trav_begin(Trav& t, const Ray& r, uint32_t start) {
     // InBoundary computes 1/dir per node; hoisting it is bit-identical.
-    if (__builtin_amdgcn_ballot_w64(!(rcp_fast_ok(r.d.x) && rcp_fast_ok(r.d.y) && rcp_fast_ok(r.d.z))) == 0) {
+    // One vote for the four reciprocals (1/dir per axis and 1/a): rcp_newton where all four values of every active
+    // lane are in its domain, else the compiler's division for all four.  The two agree wherever rcp_newton applies,
+    // so a lane's bits do not depend on the side its wave took.  The vote is the ballot of ONE compare, on the largest
+    // of the four exponent offsets: a ballot of `a && b && c` nests an exec save per term and rebuilds the lane mask
+    // (DESIGN.md §29), and 1/a used to have a vote and a branch of its own.
+    t.a = lensq(r.d);  // hittables.go:98, loop-invariant
+    const uint32_t worst = max(max(rcp_exp_off(r.d.x), rcp_exp_off(r.d.y)), max(rcp_exp_off(r.d.z), rcp_exp_off(t.a)));
+    if (__builtin_amdgcn_ballot_w64(worst > 250u) == 0) {
         t.ix = rcp_newton(r.d.x);
         t.iy = rcp_newton(r.d.y);
         t.iz = rcp_newton(r.d.z);
+        t.ra = rcp_newton(t.a);
     } else {
         t.ix = 1.0f / r.d.x;
         t.iy = 1.0f / r.d.y;
         t.iz = 1.0f / r.d.z;
+        t.ra = 1.0f / t.a;
     }
     t.nx = t.ix < 0.0f;
     t.ny = t.iy < 0.0f;
     t.nz = t.iz < 0.0f;
-    t.a = lensq(r.d);  // hittables.go:98, loop-invariant
-    t.ra = rcp_ieee(t.a);
-    t.safe = __builtin_isfinite(t.ix) && __builtin_isfinite(t.iy) && __builtin_isfinite(t.iz) &&
-             __builtin_isfinite(r.o.x) && __builtin_isfinite(r.o.y) && __builtin_isfinite(r.o.z) &&
-             t.a >= 0x1p-60f && t.a <= 0x1p60f;
-    if (FMA) t.safe = t.safe && near_fma_ok(r, t);
+    // `safe` from single compares combined with `&` (no nested tests).  FMA: near_fma_ok's bounds imply the six
+    // finite tests — an infinity or a NaN fails `<=` — so they are left out: six compares instead of twelve.
+    const bool a_ok = (t.a >= 0x1p-60f) & (t.a <= 0x1p60f);
+    if constexpr (FMA) {
+        const bool fma_ok = near_fma_ok(r, t);
+        t.safe = fma_ok & a_ok;
+    } else {
+        t.safe = (__builtin_isfinite(t.ix) != 0) & (__builtin_isfinite(t.iy) != 0) & (__builtin_isfinite(t.iz) != 0) &
+                 (__builtin_isfinite(r.o.x) != 0) & (__builtin_isfinite(r.o.y) != 0) &
+                 (__builtin_isfinite(r.o.z) != 0) & a_ok;
+    }
     t.closest = __builtin_inff();
     t.hit = -1;
     t.i = start;

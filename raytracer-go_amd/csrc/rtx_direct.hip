@@ -15,9 +15,9 @@
 // instantiation's: one per wave and counter, after the wave's last block.
 //
 // Wave votes.  The ballots here, in trav_begin and in the batched step sit where the whole wave arrives.  unit()'s
-// reciprocal and square root and the checker's parity (texture_value) are reached under a lane's own branch, as in
-// shade_hits (rtx_shade.hip): both of their forms return the same bits for every lane the short form admits, and a
-// ballot only sees the lanes that are there.
+// one vote on the squared length and the checker's parity (texture_value) are reached under a lane's own branch, as
+// in shade_hits (rtx_shade.hip): both of their forms return the same bits for every lane the short form admits, and
+// a ballot only sees the lanes that are there.
 #include "rtx_direct.h"
 
 #include "rtx_device.h"

@@ -13,12 +13,12 @@
 // Philox block, unit(dir) and the counting instantiation's reduce.  The only atomics are that reduce's: one per wave
 // and counter.
 //
-// Wave votes under a partial EXEC.  unit()'s reciprocal and square root (rcp_ieee, sqrt_rn) and the checker's parity
-// choose between a short form and the general one by a ballot of the lanes that are there; both forms return the same
-// bits for every lane the short form admits, and the ballot only sees active lanes, so a vote taken by a part of the
-// wave (the lanes of one material, the lanes still rejecting in rand_unit_on_sphere) picks a form that is right for
-// each of them.  The render's shade() takes the same votes inside the same branches.  Unit(r.dir) of Metal and
-// Dielectric is computed by the whole wave and selected per lane, as write_hit does (rtx_trace.hip).
+// Wave votes under a partial EXEC.  unit() (one vote on the squared length for both of its fast forms) and the
+// checker's parity choose between a short form and the general one by a ballot of the lanes that are there; both forms
+// return the same bits for every lane the short form admits, and the ballot only sees active lanes, so a vote taken by
+// a part of the wave (the lanes of one material, the lanes still rejecting in rand_unit_on_sphere) picks a form that
+// is right for each of them.  The render's shade() takes the same votes inside the same branches.  Unit(r.dir) of
+// Metal and Dielectric is computed by the whole wave and selected per lane, as write_hit does (rtx_trace.hip).
 #include "rtx_shade.h"
 
 #include "rtx_device.h"
