@@ -132,7 +132,7 @@ int rtx_accum_create(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const r
         a->noisy.release();
         a->adapt.release();
         delete a;
-        return fail(e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP, "the accumulator's buffers: %s", hipGetErrorString(e));
+        return hip_fail(e, "the accumulator's buffers");
     }
     *out = a;
     return RTX_OK;
@@ -142,7 +142,7 @@ int rtx_accum_add(rtx_accum* a, uint32_t count, void* hip_stream, uint32_t flags
     g_last_error.clear();
     if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
     if (count == 0) return fail(RTX_ERR_INVALID_ARG, "a pass of 0 samples");
-    if (a->n + count < a->n) return fail(RTX_ERR_INVALID_ARG, "%u + %u samples exceed 2^32 - 1", a->n, count);
+    if (int rc = check_sample_range(a->n, count)) return rc;
     if (a->adaptive)
         return fail(RTX_ERR_INVALID_ARG, "a uniform pass after an adaptive one: the tiles no longer share one n (reset first)");
     if (a->direct) return fail(RTX_ERR_INVALID_ARG, "a plain pass after a direct-light one: another estimator (reset first)");
@@ -169,7 +169,7 @@ int rtx_accum_add_adaptive(rtx_accum* a, uint32_t count, float rel_tol, uint32_t
     g_last_error.clear();
     if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
     if (count == 0) return fail(RTX_ERR_INVALID_ARG, "a pass of 0 samples");
-    if (a->n + count < a->n) return fail(RTX_ERR_INVALID_ARG, "%u + %u samples exceed 2^32 - 1", a->n, count);
+    if (int rc = check_sample_range(a->n, count)) return rc;
     if (!(rel_tol >= 0.0f)) return fail(RTX_ERR_INVALID_ARG, "rel_tol %g: a tolerance is >= 0", (double)rel_tol);
     if (a->direct) return fail(RTX_ERR_INVALID_ARG, "an adaptive pass after a direct-light one: another estimator (reset first)");
     if (int rc = accum_device(a)) return rc;
@@ -220,7 +220,7 @@ int rtx_accum_add_direct(rtx_accum* a, uint32_t count, void* hip_stream, uint32_
     g_last_error.clear();
     if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
     if (count == 0) return fail(RTX_ERR_INVALID_ARG, "a pass of 0 samples");
-    if (a->n + count < a->n) return fail(RTX_ERR_INVALID_ARG, "%u + %u samples exceed 2^32 - 1", a->n, count);
+    if (int rc = check_sample_range(a->n, count)) return rc;
     if (flags != 0u) return fail(RTX_ERR_INVALID_ARG, "direct pass flags 0x%x: must be 0", flags);
     if (a->adaptive) return fail(RTX_ERR_INVALID_ARG, "a direct-light pass after an adaptive one (reset first)");
     if (a->n != 0u && !a->direct)

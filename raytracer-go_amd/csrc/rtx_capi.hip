@@ -112,7 +112,7 @@ int rtx_scene_create_spheres(const rtx_sphere* spheres, uint32_t n_spheres, cons
     hipError_t e = rtxd::build_sphere_bvh(spheres, n_spheres, bvh_seed, bvh_draw0, s->base, &ms);
     if (e != hipSuccess) {
         delete s;
-        return fail(e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP, "GPU BVH build: %s", hipGetErrorString(e));
+        return hip_fail(e, "GPU BVH build");
     }
     if (build_ms) *build_ms = ms;
     rank_spheres(s);

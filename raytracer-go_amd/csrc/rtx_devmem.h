@@ -1,4 +1,4 @@
-// rtx_devmem.h — the two owner types of the host code's device resources.
+// rtx_devmem.h — the three owner types of the host code's device resources.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,6 +52,53 @@ public:
 private:
     int prev_ = -1;
     hipError_t err_ = hipSuccess;
+};
+
+// The device buffers of one host-pointer entry (rtx_trace, rtx_shade, ..): each of the caller's arrays with its
+// device twin for the length of the call.  Unlike DeviceBuffer this one frees in its destructor, and may: it lives in
+// the entry's own scope alone, never in static storage and never copied, so it dies on every path out of a call
+// that has just used the runtime, with the device the buffers were made on still current.
+enum class Stage { in, out, scratch };  // copied to the device before the call, back after it, neither
+struct StageItem {
+    const void* host;  // nullptr (but for scratch): an array the caller left out, which gets no buffer
+    size_t bytes;
+    Stage dir;
+};
+template <size_t N>
+class Staging {
+public:
+    explicit Staging(const StageItem (&items)[N]) {
+        for (size_t i = 0; i < N; ++i) item_[i] = items[i];
+    }
+    ~Staging() {
+        for (DeviceBuffer& b : buf_) b.release();
+    }
+    Staging(const Staging&) = delete;
+    Staging& operator=(const Staging&) = delete;
+    template <class T>
+    T* dev(size_t i) const { return buf_[i].template as<T>(); }
+
+    // Reserves the buffers, copies the inputs in, runs call() (the _device entry on the null stream; *rc: its RTX_*
+    // code) and after an RTX_OK (0) copies the outputs out (blocking copies: after the kernels).  Returns the first
+    // failure of a reserve or a copy; call()'s code, where it is not 0, is the one to report.
+    template <class F>
+    hipError_t run(F&& call, int* rc) {
+        hipError_t e = hipSuccess;
+        for (size_t i = 0; i < N && e == hipSuccess; ++i)
+            if (item_[i].host || item_[i].dir == Stage::scratch) e = buf_[i].reserve(item_[i].bytes);
+        for (size_t i = 0; i < N && e == hipSuccess; ++i)
+            if (item_[i].host && item_[i].dir == Stage::in)
+                e = hipMemcpy(buf_[i].ptr, item_[i].host, item_[i].bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess || (*rc = call()) != 0) return e;
+        for (size_t i = 0; i < N && e == hipSuccess; ++i)
+            if (item_[i].host && item_[i].dir == Stage::out)
+                e = hipMemcpy(const_cast<void*>(item_[i].host), buf_[i].ptr, item_[i].bytes, hipMemcpyDeviceToHost);
+        return e;
+    }
+
+private:
+    StageItem item_[N];
+    DeviceBuffer buf_[N];
 };
 
 }  // namespace rtxd

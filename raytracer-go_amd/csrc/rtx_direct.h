@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/rtx.h"
+#include "rtx_walk.h"
 
 namespace rtxd {
 // Device counters of a counting call, in memory of the scene copy's own (never the render's, the trace's or the shade's).
@@ -16,11 +17,7 @@ constexpr uint32_t DIRECT_EVENT = 0x40000000u;
 // One launch: records [0, n) of the three arrays, n <= DIRECT_LAUNCH_MAX (record indices are 32-bit).
 constexpr uint64_t DIRECT_LAUNCH_MAX = 1ull << 30;
 struct DirectParams {
-    const float4* entries;  // a trace layout (rtx_layout.h): n_entries + 1 'a' halves, as many 'b', 4 * n_quads
-    uint32_t n_entries;
-    uint32_t n_quads;
-    uint32_t start;     // walk position of the root
-    uint32_t prim_end;  // scene in the LDS copy: its primitives are stored below this position
+    WalkScene scene;  // a trace layout
     const rtx_material* materials;  // the device forms of DeviceCopy
     const rtx_texture* textures;
     const uint32_t* texels;
@@ -44,16 +41,9 @@ hipError_t launch_direct(const DirectParams& p, bool count, bool noise, hipStrea
 // width * rows pixels (at most 2^32 - 1) by the estimator of DESIGN.md §37, folded into the accumulator's tile-major
 // moments acc_s and acc_q (slot = tile * 64 + lane, 3 floats each; rtx_kernel.hip accumulate_samples' layout).
 struct DirectPathParams {
-    rtx_camera cam;
-    uint64_t seed;
-    uint32_t x0, y0, width, rows, rank, world, stripe_log2;
-    uint32_t k0, kn;
+    Shard shard;
+    WalkScene scene;        // a trace layout
     uint32_t tile_w_log2;   // the accumulator's tiles: 2^tile_w_log2 wide, 64 pixels
-    const float4* entries;  // a trace layout (rtx_layout.h), as TraceParams'
-    uint32_t n_entries;
-    uint32_t n_quads;
-    uint32_t start;
-    uint32_t prim_end;
     uint32_t refill;        // parked lanes with work at which a wave runs its fold step (1..64)
     uint32_t prim_batch;    // primitive tests wait for this many lanes (trav_step_batched)
     uint32_t want_uv;       // the scene has an image texture: sphere hits need (u, v)

@@ -4,8 +4,9 @@
 //   sample   the contract of include/rtx.h ("direct light sampling"), computed with the render's own device functions
 //            (rtx_device.h: the Philox block, texture_value, sphere_uv, unit, and the unit-sphere loop of
 //            rand_unit_on_sphere with its attempts on blocks 1, 2, ..): float32, each operation rounded, no contraction.
-//   shadow   trace_rays' any-hit walk (rtx_trace.hip) over the same trace layout: trav_begin, then the batched step with
-//            the ray's own tmin and the bound starting at tmax = 0.999, a lane parking at its first accepted primitive.
+//   shadow   trace_rays' any-hit walk (rtx_trace.hip) over the same trace layout: trav_begin, then walk_steps
+//            (rtx_walk.h) with the ray's own tmin and the bound starting at tmax = 0.999, a lane parking at its first
+//            accepted primitive.
 //
 // Work distribution: no cross-wave state.  Wave w owns records [w * range, (w + 1) * range) and takes them 64 at a
 // time, the plain form of trace_rays (refill = 64): the block's samples are computed, its shadow rays are walked
@@ -20,14 +21,11 @@
 // a ballot only sees the lanes that are there.
 #include "rtx_direct.h"
 
-#include "rtx_device.h"
 #include "rtx_trace.h"
+#include "rtx_walk.h"
 
 namespace rtxd {
 namespace {
-
-constexpr int DIRECT_WAVES = 8;        // waves per workgroup (one LDS copy of the scene each)
-constexpr uint32_t DIRECT_STEPS = 4;   // walk steps between two votes on the parked lanes
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
@@ -121,27 +119,12 @@ __device__ __forceinline__ LightSample light_sample(const LightTables& p, const 
 // COUNT: the counting instantiation (sampled, visible, rng_draws).  QUADS: the scene holds quads.  FIXED: the scene
 // in the workgroup's LDS copy (scene_ref_fixed), else read from HBM.  NOISE: the scene has a Perlin texture.
 template <bool COUNT, bool QUADS, bool FIXED, bool NOISE>
-__global__ __launch_bounds__(64 * DIRECT_WAVES) void direct_lights(DirectParams p) {
+__global__ __launch_bounds__(64 * WALK_WAVES) void direct_lights(DirectParams p) {
     extern __shared__ float4 lds_entries[];
-    SceneRef E;
-    if constexpr (FIXED) {
-        // scene_ref_fixed: the walk addresses LDS directly, so the copy must start at 0
-        if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) float4*)lds_entries != 0u) __builtin_trap();
-        const uint32_t m = p.n_entries + 1, nq4 = 4 * p.n_quads;
-        for (uint32_t i = threadIdx.x; i < m; i += 64 * DIRECT_WAVES) {
-            lds_entries[i] = p.entries[i];
-            lds_entries[LDS_B / 16 + i] = p.entries[m + i];
-        }
-        for (uint32_t i = threadIdx.x; i < nq4; i += 64 * DIRECT_WAVES) lds_entries[LDS_B / 16 + m + i] = p.entries[2 * m + i];
-        __syncthreads();
-        E = scene_ref_fixed(lds_entries, p.n_entries, p.n_quads, 0u, 0u);
-        E.prim_end = p.prim_end;
-    } else {
-        E = scene_ref(p.entries, p.n_entries, nullptr);
-    }
-    const uint32_t end = 16 * p.n_entries;  // the sentinel's position
+    const SceneRef E = stage_scene<WALK_WAVES, FIXED>(lds_entries, p.scene);
+    const uint32_t end = walk_end(p.scene);
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * DIRECT_WAVES + (threadIdx.x >> 6));
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * WALK_WAVES + (threadIdx.x >> 6));
     const uint64_t first = (uint64_t)wave * p.range;
     if (first >= p.n) return;  // (the whole wave)
     const uint32_t last = (uint32_t)(first + p.range < p.n ? first + p.range : p.n);  // the wave's records: [first, last)
@@ -180,28 +163,12 @@ __global__ __launch_bounds__(64 * DIRECT_WAVES) void direct_lights(DirectParams 
         const Ray r = sampled ? Ray{pt, w} : Ray{v3(0.0f, 0.0f, 0.0f), v3(1.0f, 1.0f, 1.0f)};
         const float tmin = 0.001f;
         Trav t;
-        trav_begin(t, r, sampled ? p.start : end);
+        trav_begin(t, r, sampled ? p.scene.start : end);
         t.safe = t.safe && tmin >= 0x1p-126f;  // as trace_rays: the fast step forms need every accepted root normal
         t.closest = 0.999f;                    // the running bound starts at the ray's tmax
         Counters cnt{0, 0, 0, 0, 0, 0, 0};
-        while (ballot(t.i < end) != 0) {
-            uint32_t idle = 0;
-            if (ballot(!t.safe && t.i < end) == 0) {
-#pragma unroll
-                for (uint32_t s = 0; s < DIRECT_STEPS; ++s) {
-                    trav_step_batched<false, QUADS, FIXED, false, true>(t, r, E, cnt, end, p.prim_batch, idle,
-                                                                        V3{0.0f, 0.0f, 0.0f}, tmin);
-                    if (t.hit >= 0) t.i = end;
-                }
-            } else {
-#pragma unroll
-                for (uint32_t s = 0; s < DIRECT_STEPS; ++s) {
-                    trav_step_batched<false, QUADS, FIXED, false, false>(t, r, E, cnt, end, p.prim_batch, idle,
-                                                                         V3{0.0f, 0.0f, 0.0f}, tmin);
-                    if (t.hit >= 0) t.i = end;
-                }
-            }
-        }
+        while (ballot(t.i < end) != 0)
+            t = walk_steps<WALK_STEPS, false, QUADS, FIXED>(t, r, E, cnt, end, p.prim_batch, tmin, true);
         const bool visible = sampled && t.hit < 0;
         if (visible) flags |= RTX_DIRECT_VISIBLE;
 
@@ -233,102 +200,38 @@ __global__ __launch_bounds__(64 * DIRECT_WAVES) void direct_lights(DirectParams 
 // direct_paths is guide_images' loop (rtx_guides.hip) carried through a whole path.  A wave owns one 64-pixel tile of the
 // accumulator's S / Q layout and a lane owns a pixel.  A lane's walk is either a closest-hit walk (a path segment) or a
 // shadow walk; a lane whose walk has ended is parked on the end sentinel.  Once `refill` lanes are parked with work (or
-// no lane walks) the whole wave runs one FOLD STEP: every lane forms the hit record of its walk as write_hit does
-// (rtx_trace.hip), shades it with shade_hits' per-record code (rtx_shade.hip) and samples a light (light_sample); the
+// no lane walks) the whole wave runs one FOLD STEP: every lane forms the hit record of its walk (hit_record,
+// rtx_walk.h), shades it with shade_hits' per-record code (rtx_shade.hip) and samples a light (light_sample); the
 // parked lanes then apply the estimator of DESIGN.md §37 to their own result and start the shadow ray, or the bounce
 // ray when nothing was sampled, or the next sample's camera ray; a parked shadow walk adds or drops its radiance and
 // starts the saved bounce.  No ray, hit, bounce or path state goes through memory; no atomics; nothing spins (samples,
 // segments and walk positions only move forward); every vote (here, in trav_begin, unit, the batched step) sits where
 // the whole wave arrives, except those inside a lane's own material branch, as in shade_hits.
-struct PathHit {
-    bool hit, front;
-    uint32_t mi;
-    V3 pt, n;
-    float u, v;
-};
-
-// NewHitInfo of a lane's finished closest walk, as write_hit forms it (computed by every lane: unit's votes).
-template <bool QUADS>
-__device__ __forceinline__ PathHit path_hit(const SceneRef E, const Trav& t, const Ray& r, const bool want_uv) {
-    PathHit h;
-    h.hit = t.hit >= 0;
-    const uint32_t e = h.hit ? (uint32_t)t.hit : 0u;  // (a miss reads entry 0 and drops it)
-    const float4 sa = E.a[e];
-    const float4 sb = E.b[e];
-    const bool quad = QUADS && h.hit && __float_as_int(sb.w) == RTX_E_QUAD;
-    h.pt = add(scale(r.d, t.closest), r.o);                                      // ray.go:25-30
-    const V3 ns = unit(scale(sub(h.pt, v3(sa.x, sa.y, sa.z)), sa.w));            // hittables.go:119-120
-    h.n = ns;
-    h.mi = 0u;
-    h.u = h.v = 0.0f;
-    if (quad) {
-        const uint32_t qi = 4u * (uint32_t)__float_as_int(sb.x);
-        const float4 q0 = E.q[qi];
-        h.mi = (uint32_t)__float_as_int(q0.w);
-        h.n = v3(sa.x, sa.y, sa.z);                                              // q.normal
-        if (want_uv) {  // (alpha, beta) as quad_test formed them (hittables.go:181-183)
-            const float4 q1 = E.q[qi + 1], q2 = E.q[qi + 2], q3 = E.q[qi + 3];
-            const V3 php = sub(h.pt, v3(q0.x, q0.y, q0.z));
-            const V3 w = v3(q3.x, q3.y, q3.z);
-            h.u = dot(w, cross(php, v3(q2.x, q2.y, q2.z)));
-            h.v = dot(w, cross(v3(q1.x, q1.y, q1.z), php));
-        }
-    } else if (h.hit) {
-        h.mi = RTX_DEV_SPHERE_MATERIAL(__float_as_int(sb.w));
-        if (want_uv) {                                                           // hittables.go:122-126
-            const UV uv = sphere_uv(h.n.x, h.n.y, h.n.z);
-            h.u = uv.u;
-            h.v = uv.v;
-        }
-    }
-    h.front = dot(r.d, h.n) < 0.0f;                                              // hittables.go:23
-    if (!h.front) h.n = scale(h.n, -1.0f);                                       // :24-26
-    return h;
-}
-
 // QUADS: the scene holds quads.  FIXED: the scene in the workgroup's LDS copy, else read from HBM.  NOISE: the scene has
 // a Perlin texture.
 template <bool QUADS, bool FIXED, bool NOISE>
-__global__ __launch_bounds__(64 * DIRECT_WAVES) void direct_paths(DirectPathParams p) {
+__global__ __launch_bounds__(64 * WALK_WAVES) void direct_paths(DirectPathParams p) {
     extern __shared__ float4 lds_entries[];
-    SceneRef E;
-    if constexpr (FIXED) {
-        // scene_ref_fixed: the walk addresses LDS directly, so the copy must start at 0
-        if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) float4*)lds_entries != 0u) __builtin_trap();
-        const uint32_t m = p.n_entries + 1, nq4 = 4 * p.n_quads;
-        for (uint32_t i = threadIdx.x; i < m; i += 64 * DIRECT_WAVES) {
-            lds_entries[i] = p.entries[i];
-            lds_entries[LDS_B / 16 + i] = p.entries[m + i];
-        }
-        for (uint32_t i = threadIdx.x; i < nq4; i += 64 * DIRECT_WAVES) lds_entries[LDS_B / 16 + m + i] = p.entries[2 * m + i];
-        __syncthreads();
-        E = scene_ref_fixed(lds_entries, p.n_entries, p.n_quads, 0u, 0u);
-        E.prim_end = p.prim_end;
-    } else {
-        E = scene_ref(p.entries, p.n_entries, nullptr);
-    }
-    const uint32_t end = 16 * p.n_entries;  // the sentinel's position
+    const SceneRef E = stage_scene<WALK_WAVES, FIXED>(lds_entries, p.scene);
+    const uint32_t end = walk_end(p.scene);
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t twl = p.tile_w_log2, tw = 1u << twl, th = 64u >> twl;
-    const uint32_t tiles_x = tiles_x_of(p.width, twl);
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * DIRECT_WAVES + (threadIdx.x >> 6));
-    if (wave >= tiles_x * tiles_y_of(p.rows, twl)) return;  // (the whole wave)
-    const uint32_t tile_y = wave / tiles_x, tile_x = wave - tile_y * tiles_x;
-    const uint32_t px = tile_x * tw + (lane & (tw - 1u)), py = tile_y * th + (lane >> twl);
-    const bool live = px < p.width && py < p.rows;  // (a lane outside a ragged tile computes on the nearest pixel)
-    const uint32_t xx = px < p.width ? px : p.width - 1u, lr = py < p.rows ? py : p.rows - 1u;
-    const uint32_t x = p.x0 + xx, y = p.y0 + region_row(lr, p.rank, p.world, p.stripe_log2);
-    const uint32_t pixel = y * p.cam.image_width + x;  // the GLOBAL pixel index: the RNG's counter word
-    const V3 base = pixel_base(p.cam, x, y);
-    const uint32_t s0 = (uint32_t)p.seed, s1 = (uint32_t)(p.seed >> 32);
+    const Shard& sh = p.shard;
+    const uint32_t twl = p.tile_w_log2;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * WALK_WAVES + (threadIdx.x >> 6));
+    if (wave >= tiles_x_of(sh.width, twl) * tiles_y_of(sh.rows, twl)) return;  // (the whole wave)
+    const TilePixel tp = tile_pixel(sh, twl, wave, lane);
+    const bool live = tp.live;  // (a lane outside a ragged tile computes on the nearest pixel)
+    const uint32_t pixel = tp.pixel;
+    const V3 base = tp.base;
+    const uint32_t s0 = (uint32_t)sh.seed, s1 = (uint32_t)(sh.seed >> 32);
     const LightTables tabs{p.materials, p.textures, p.texels, p.lights, p.n_lights};
-    const V3 bg = v3(p.cam.background[0], p.cam.background[1], p.cam.background[2]);
+    const V3 bg = v3(sh.cam.background[0], sh.cam.background[1], sh.cam.background[2]);
     const V3 zero = v3(0.0f, 0.0f, 0.0f), one = v3(1.0f, 1.0f, 1.0f);
-    const uint32_t depth = p.cam.max_depth;
+    const uint32_t depth = sh.cam.max_depth;
     const bool want_uv = p.want_uv != 0u;
 
-    uint32_t k = p.k0;                  // the lane's sample
-    const uint32_t kend = p.k0 + p.kn;  // (at most 2^32 - 1: the entry's check)
+    uint32_t k = sh.k0;                   // the lane's sample
+    const uint32_t kend = sh.k0 + sh.kn;  // (at most 2^32 - 1: the entry's check)
     uint32_t seg = 0, cam_draws = 0;
     bool shadow = false, diffuse = false;
     V3 T = one, Lc = zero, pending = zero, bounce = zero;  // pending: T * radiance of the walking shadow ray; bounce: the saved direction
@@ -343,10 +246,10 @@ __global__ __launch_bounds__(64 * DIRECT_WAVES) void direct_paths(DirectPathPara
     Ray r;
     {
         const PathRng rng{s0, s1, pixel, k};
-        r = camera_ray<false>(p.cam, base, rng, rng.block(0, 0), cam_draws);
+        r = camera_ray<false>(sh.cam, base, rng, rng.block(0, 0), cam_draws);
     }
     Trav t{};
-    trav_begin(t, r, p.start);
+    trav_begin(t, r, p.scene.start);
     Counters cnt{0, 0, 0, 0, 0, 0, 0};
 
     for (;;) {
@@ -358,7 +261,7 @@ __global__ __launch_bounds__(64 * DIRECT_WAVES) void direct_paths(DirectPathPara
             // -- the fold step, whole wave.  What follows is computed by every lane on its own walk and kept where
             //    `seg_end` (a parked closest walk) or `sh_end` (a parked shadow walk) says so.
             const bool seg_end = pend && !shadow, sh_end = pend && shadow;
-            const PathHit h = path_hit<QUADS>(E, t, r, want_uv);
+            const HitRecord h = hit_record<QUADS>(E, t, r, want_uv);
             const bool hit = seg_end && h.hit && h.mi < p.n_materials;
             const float4* mp = reinterpret_cast<const float4*>(p.materials + (hit ? h.mi : 0u));
             const float4 m0 = mp[0], m1 = mp[1];
@@ -467,29 +370,31 @@ __global__ __launch_bounds__(64 * DIRECT_WAVES) void direct_paths(DirectPathPara
             }
             // the next sample's camera ray (the whole wave: its rejection loop and unit's votes)
             const PathRng crng{s0, s1, pixel, k};
-            const Ray cr = camera_ray<false>(p.cam, base, crng, crng.block(0, 0), cam_draws);
+            const Ray cr = camera_ray<false>(sh.cam, base, crng, crng.block(0, 0), cam_draws);
             Ray nr = Ray{next_o, next_d};
             if (sample_done) nr = cr;
             const bool go = start_shadow || start_bounce || (sample_done && k < kend);
             Trav nt;
-            trav_begin(nt, nr, go ? p.start : end);  // (whole wave: its votes)
+            trav_begin(nt, nr, go ? p.scene.start : end);  // (whole wave: its votes)
             if (start_shadow) nt.closest = 0.999f;   // the shadow ray's tmax; tmin = 0.001 either way
             if (pend) {
                 r = nr;
                 t = nt;  // (out of samples: parked on the sentinel for good)
             }
         }
-        // DIRECT_STEPS walk steps: the med3 / div_by forms when every walking lane's ray is safe (traverse_phase)
+        // WALK_STEPS walk steps, written out here: walk_steps (rtx_walk.h) with this kernel's per-lane park flag moved
+        // the hot loop's code and add_direct measured 0.45 % longer, past the parent's own spread.
+        // The med3 / div_by forms when every walking lane's ray is safe (traverse_phase).
         uint32_t idle = 0;
         if (ballot(!t.safe && t.i < end) == 0) {
 #pragma unroll
-            for (uint32_t s = 0; s < DIRECT_STEPS; ++s) {
+            for (uint32_t s = 0; s < WALK_STEPS; ++s) {
                 trav_step_batched<false, QUADS, FIXED, false, true>(t, r, E, cnt, end, p.prim_batch, idle);
                 if (shadow && t.hit >= 0) t.i = end;  // any-hit: park at the first accepted primitive
             }
         } else {
 #pragma unroll
-            for (uint32_t s = 0; s < DIRECT_STEPS; ++s) {
+            for (uint32_t s = 0; s < WALK_STEPS; ++s) {
                 trav_step_batched<false, QUADS, FIXED, false, false>(t, r, E, cnt, end, p.prim_batch, idle);
                 if (shadow && t.hit >= 0) t.i = end;
             }
@@ -507,9 +412,9 @@ __global__ __launch_bounds__(64 * DIRECT_WAVES) void direct_paths(DirectPathPara
 
 template <bool QUADS, bool FIXED>
 hipError_t launch_paths_noise(const DirectPathParams& p, bool noise, hipStream_t stream) {
-    const size_t shmem = FIXED ? LDS_B + (p.n_entries + 1) * 16 + p.n_quads * 64 : 0;  // trace_lds_bytes (rtx_trace.hip)
-    const uint64_t tiles = (uint64_t)tiles_x_of(p.width, p.tile_w_log2) * tiles_y_of(p.rows, p.tile_w_log2);
-    const dim3 grid((uint32_t)((tiles + DIRECT_WAVES - 1) / DIRECT_WAVES)), block(64 * DIRECT_WAVES);
+    const size_t shmem = FIXED ? walk_lds_bytes(p.scene.n_entries, p.scene.n_quads) : 0;
+    const uint64_t tiles = (uint64_t)tiles_x_of(p.shard.width, p.tile_w_log2) * tiles_y_of(p.shard.rows, p.tile_w_log2);
+    const dim3 grid((uint32_t)((tiles + WALK_WAVES - 1) / WALK_WAVES)), block(64 * WALK_WAVES);
     if (noise) hipLaunchKernelGGL((direct_paths<QUADS, FIXED, true>), grid, block, shmem, stream, p);
     else hipLaunchKernelGGL((direct_paths<QUADS, FIXED, false>), grid, block, shmem, stream, p);
     return hipGetLastError();
@@ -517,9 +422,9 @@ hipError_t launch_paths_noise(const DirectPathParams& p, bool noise, hipStream_t
 
 template <bool COUNT, bool QUADS, bool FIXED>
 hipError_t launch_noise(const DirectParams& p, bool noise, hipStream_t stream) {
-    const size_t shmem = FIXED ? LDS_B + (p.n_entries + 1) * 16 + p.n_quads * 64 : 0;  // trace_lds_bytes (rtx_trace.hip)
+    const size_t shmem = FIXED ? walk_lds_bytes(p.scene.n_entries, p.scene.n_quads) : 0;
     const uint64_t waves = ((uint64_t)p.n + p.range - 1) / p.range;
-    const dim3 grid((uint32_t)((waves + DIRECT_WAVES - 1) / DIRECT_WAVES)), block(64 * DIRECT_WAVES);
+    const dim3 grid((uint32_t)((waves + WALK_WAVES - 1) / WALK_WAVES)), block(64 * WALK_WAVES);
     if (noise) hipLaunchKernelGGL((direct_lights<COUNT, QUADS, FIXED, true>), grid, block, shmem, stream, p);
     else hipLaunchKernelGGL((direct_lights<COUNT, QUADS, FIXED, false>), grid, block, shmem, stream, p);
     return hipGetLastError();
@@ -527,8 +432,8 @@ hipError_t launch_noise(const DirectParams& p, bool noise, hipStream_t stream) {
 
 template <bool COUNT>
 hipError_t launch_count(const DirectParams& p, bool noise, hipStream_t stream) {
-    const bool fixed = trace_placement(p.n_entries, p.n_quads) == RTX_SCENE_IN_LDS;
-    if (p.n_quads) return fixed ? launch_noise<COUNT, true, true>(p, noise, stream) : launch_noise<COUNT, true, false>(p, noise, stream);
+    const bool fixed = trace_placement(p.scene.n_entries, p.scene.n_quads) == RTX_SCENE_IN_LDS;
+    if (p.scene.n_quads) return fixed ? launch_noise<COUNT, true, true>(p, noise, stream) : launch_noise<COUNT, true, false>(p, noise, stream);
     return fixed ? launch_noise<COUNT, false, true>(p, noise, stream) : launch_noise<COUNT, false, false>(p, noise, stream);
 }
 
@@ -536,7 +441,7 @@ hipError_t launch_count(const DirectParams& p, bool noise, hipStream_t stream) {
 
 hipError_t launch_direct(const DirectParams& p, bool count, bool noise, hipStream_t stream) {
     if (p.n == 0) return hipSuccess;
-    if (p.n > DIRECT_LAUNCH_MAX || p.range == 0 || p.range % 64u != 0 || !p.hits || !p.keys || !p.out || !p.entries ||
+    if (p.n > DIRECT_LAUNCH_MAX || p.range == 0 || p.range % 64u != 0 || !p.hits || !p.keys || !p.out || !p.scene.entries ||
         !p.materials || !p.textures || !p.texels || (p.n_lights && !p.lights) || p.n_lights > (1u << 24) ||
         (count && !p.counters))
         return hipErrorInvalidValue;
@@ -544,14 +449,15 @@ hipError_t launch_direct(const DirectParams& p, bool count, bool noise, hipStrea
 }
 
 hipError_t launch_direct_paths(const DirectPathParams& p, bool noise, hipStream_t stream) {
-    const uint64_t P = (uint64_t)p.width * p.rows;
-    if (P == 0 || p.kn == 0) return hipSuccess;
-    if (P > 0xFFFFFFFFull || (uint64_t)p.k0 + p.kn > 0xFFFFFFFFull || p.tile_w_log2 > 6u || p.refill == 0 || p.refill > 64u ||
-        p.world == 0 || p.rank >= p.world || !p.entries || !p.materials || !p.textures || !p.texels || !p.acc_s || !p.acc_q ||
+    const Shard& sh = p.shard;
+    const uint64_t P = (uint64_t)sh.width * sh.rows;
+    if (P == 0 || sh.kn == 0) return hipSuccess;
+    if (P > 0xFFFFFFFFull || (uint64_t)sh.k0 + sh.kn > 0xFFFFFFFFull || p.tile_w_log2 > 6u || p.refill == 0 || p.refill > 64u ||
+        sh.world == 0 || sh.rank >= sh.world || !p.scene.entries || !p.materials || !p.textures || !p.texels || !p.acc_s || !p.acc_q ||
         (p.n_lights && !p.lights) || p.n_lights > (1u << 24))
         return hipErrorInvalidValue;
-    const bool fixed = trace_placement(p.n_entries, p.n_quads) == RTX_SCENE_IN_LDS;
-    if (p.n_quads) return fixed ? launch_paths_noise<true, true>(p, noise, stream) : launch_paths_noise<true, false>(p, noise, stream);
+    const bool fixed = trace_placement(p.scene.n_entries, p.scene.n_quads) == RTX_SCENE_IN_LDS;
+    if (p.scene.n_quads) return fixed ? launch_paths_noise<true, true>(p, noise, stream) : launch_paths_noise<true, false>(p, noise, stream);
     return fixed ? launch_paths_noise<false, true>(p, noise, stream) : launch_paths_noise<false, false>(p, noise, stream);
 }
 

@@ -16,18 +16,8 @@ constexpr uint32_t DIRECT_FLAGS = RTX_DIRECT_COUNTERS;
 // The checks of both entries that need no device.  *empty: nothing to do (n == 0).
 int check_direct(const rtx_scene* s, const void* hits, const void* keys, uint64_t n, const void* out, uint32_t flags,
                  bool* empty) {
-    *empty = false;
-    if (!s) return fail(RTX_ERR_INVALID_ARG, "NULL scene");
-    if (flags & ~DIRECT_FLAGS) return fail(RTX_ERR_INVALID_ARG, "unknown direct flags 0x%x", flags & ~DIRECT_FLAGS);
-    if (n == 0) {
-        *empty = true;
-        return RTX_OK;
-    }
-    if (!hits || !keys || !out) return fail(RTX_ERR_INVALID_ARG, "NULL argument");
-    if (((uintptr_t)hits | (uintptr_t)keys | (uintptr_t)out) & 15u)
-        return fail(RTX_ERR_INVALID_ARG, "hits, keys and light samples must be aligned to 16 B");
-    if (n > (uint64_t)std::numeric_limits<size_t>::max() / sizeof(rtx_direct_sample)) return fail(RTX_ERR_INVALID_ARG, "too many records");
-    return RTX_OK;
+    return check_batch(s, flags, DIRECT_FLAGS, "direct", n, sizeof(rtx_direct_sample),
+                       {{hits, "hits"}, {keys, "keys"}, {out, "light samples"}}, empty);
 }
 
 // What a call on copy c needs beside the trace layout (s->mu held, current device = c's), made on first use: the
@@ -45,14 +35,7 @@ int ensure_direct(rtx_scene* s, DeviceCopy* c) {
             }
         }
     }
-    HIP_TRY(c->direct_counters.reserve(rtxd::DIRECT_COUNTER_SLOTS * sizeof(unsigned long long)));
-    if (!c->dev0) HIP_TRY(hipEventCreate(&c->dev0));
-    if (!c->dev1) HIP_TRY(hipEventCreate(&c->dev1));
-    return RTX_OK;
-}
-
-int hip_fail(hipError_t e, const char* what) {
-    return fail(e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    return c->direct.ensure(rtxd::DIRECT_COUNTER_SLOTS);
 }
 
 }  // namespace
@@ -63,34 +46,18 @@ namespace rtxh {
 // [first, first + count) of the region by direct_paths into the tile-major moments acc_s / acc_q.
 int direct_pass_locked(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const rtx_region* region, uint32_t tile_w_log2,
                        uint32_t first, uint32_t count, float* acc_s, float* acc_q, hipStream_t stream, rtx_stats* stats) {
+    DeviceCopy* c = nullptr;
     int cur = 0;
-    HIP_TRY(hipGetDevice(&cur));
-    const auto it = s->copies.find(cur);
-    if (it == s->copies.end()) return fail(RTX_ERR_INVALID_ARG, "the scene has no copy on the current device %d", cur);
-    DeviceCopy* c = it->second.get();
+    if (int rc = current_copy(s, &c, &cur)) return rc;
     const uint32_t oct = rtx_camera_octant(cam);
     const DeviceLayout* lay = nullptr;
     if (int rc = ensure_trace(s, c, oct, &lay)) return rc;
     if (int rc = ensure_direct(s, c)) return rc;
     rtxd::DirectPathParams p;
     std::memset(&p, 0, sizeof(p));
-    p.cam = *cam;
-    p.seed = seed;
-    p.x0 = region->x0;
-    p.y0 = region->y0;
-    p.width = region->width;
-    p.rows = region_rows(region);
-    p.rank = region->rank;
-    p.world = region->world;
-    p.stripe_log2 = region->stripe > 1u ? (uint32_t)(31 - __builtin_clz(region->stripe)) : 0u;
-    p.k0 = first;
-    p.kn = count;
+    p.shard = shard_of(cam, seed, region, first, count);
+    p.scene = walk_scene(s, lay);
     p.tile_w_log2 = tile_w_log2;
-    p.entries = lay->entries.as<const float4>();
-    p.n_entries = lay->n_entries;
-    p.n_quads = (uint32_t)(s->quadtab.size() / 16);
-    p.start = lay->start;
-    p.prim_end = lay->prim_end;
     p.want_uv = s->has_image ? 1u : 0u;
     p.materials = c->materials.as<const rtx_material>();
     p.textures = c->textures.as<const rtx_texture>();
@@ -109,17 +76,16 @@ int direct_pass_locked(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const
         Scratch& scr = g_scratch[cur];
         if (!scr.last) HIP_TRY(hipEventCreateWithFlags(&scr.last, hipEventDisableTiming));
         else HIP_TRY(hipStreamWaitEvent(stream, scr.last, 0));
-        if (stats) HIP_TRY(hipEventRecord(c->dev0, stream));
+        if (int rc = c->direct.begin(false, stats != nullptr, stream)) return rc;
         if (const hipError_t e = rtxd::launch_direct_paths(p, s->has_noise, stream)) return hip_fail(e, "direct pass launch failed");
-        if (stats) HIP_TRY(hipEventRecord(c->dev1, stream));
         HIP_TRY(hipEventRecord(scr.last, stream));
     }
     if (!stats) return RTX_OK;
-    HIP_TRY(hipEventSynchronize(c->dev1));
+    // (the closing event follows scr.last's record, outside the lock: no kernel runs between the two)
     float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->dev0, c->dev1));
+    if (int rc = c->direct.end(stream, &ms)) return rc;
     std::memset(stats, 0, sizeof(*stats));
-    stats->samples = (uint64_t)p.rows * p.width * count;
+    stats->samples = (uint64_t)p.shard.rows * p.shard.width * count;
     stats->kernel_ms = ms;
     stats->sample_chunks = 1;
     stats->walk_layout = s->rebuilt ? oct : RTX_LAYOUT_REFERENCE;
@@ -138,11 +104,8 @@ int rtx_direct_device(rtx_scene* s, uint64_t seed, const rtx_hit* d_hits, const 
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (empty) return RTX_OK;
     std::lock_guard<std::mutex> lk(s->mu);
-    int cur = 0;
-    HIP_TRY(hipGetDevice(&cur));
-    const auto it = s->copies.find(cur);
-    if (it == s->copies.end()) return fail(RTX_ERR_INVALID_ARG, "the scene has no copy on the current device %d", cur);
-    DeviceCopy* c = it->second.get();
+    DeviceCopy* c = nullptr;
+    if (int rc = current_copy(s, &c)) return rc;
     // (a shadow ray has no camera to hint an octant with: every hint gives the same hits, so octant 0's layout)
     const DeviceLayout* lay = nullptr;
     if (int rc = ensure_trace(s, c, 0u, &lay)) return rc;
@@ -151,11 +114,7 @@ int rtx_direct_device(rtx_scene* s, uint64_t seed, const rtx_hit* d_hits, const 
     const bool count = stats && (flags & RTX_DIRECT_COUNTERS);
     rtxd::DirectParams p;
     std::memset(&p, 0, sizeof(p));
-    p.entries = lay->entries.as<const float4>();
-    p.n_entries = lay->n_entries;
-    p.n_quads = (uint32_t)(s->quadtab.size() / 16);
-    p.start = lay->start;
-    p.prim_end = lay->prim_end;
+    p.scene = walk_scene(s, lay);
     p.materials = c->materials.as<const rtx_material>();
     p.textures = c->textures.as<const rtx_texture>();
     p.texels = c->texels.as<const uint32_t>();
@@ -163,31 +122,30 @@ int rtx_direct_device(rtx_scene* s, uint64_t seed, const rtx_hit* d_hits, const 
     p.n_lights = (uint32_t)s->lights.size();
     p.lights = c->lights.as<const float4>();
     p.seed = seed;
-    p.counters = c->direct_counters.as<unsigned long long>();
+    p.counters = c->direct.slots();
     // A/B knobs (read per call): records per wave, the lanes a primitive test waits for
     p.range = env_knob("RTX_DIRECT_RANGE", 256, 64, 1 << 20) / 64u * 64u;
     p.prim_batch = env_knob("RTX_DIRECT_PRIM_BATCH", 16, 1, 65);
     // records per launch (32-bit record indices; RTX_DIRECT_LAUNCH_RECORDS: tests of the cut)
     const uint64_t per_launch = env_knob("RTX_DIRECT_LAUNCH_RECORDS", (long)rtxd::DIRECT_LAUNCH_MAX, 64, (long)rtxd::DIRECT_LAUNCH_MAX);
-    if (count) HIP_TRY(hipMemsetAsync(c->direct_counters.ptr, 0, c->direct_counters.bytes, stream));
-    if (stats) HIP_TRY(hipEventRecord(c->dev0, stream));
-    for (uint64_t off = 0; off < n; off += per_launch) {
-        p.hits = d_hits + off;
-        p.keys = d_keys + off;
-        p.out = d_out + off;
-        p.n = (uint32_t)std::min<uint64_t>(per_launch, n - off);
-        if (const hipError_t e = rtxd::launch_direct(p, count, s->has_noise, stream)) return hip_fail(e, "direct launch failed");
-    }
+    if (int rc = c->direct.begin(count, stats != nullptr, stream)) return rc;
+    if (int rc = for_launches(n, per_launch, [&](uint64_t off, uint32_t m) {
+            p.hits = d_hits + off;
+            p.keys = d_keys + off;
+            p.out = d_out + off;
+            p.n = m;
+            const hipError_t e = rtxd::launch_direct(p, count, s->has_noise, stream);
+            return e == hipSuccess ? RTX_OK : hip_fail(e, "direct launch failed");
+        }))
+        return rc;
     if (!stats) return RTX_OK;
-    HIP_TRY(hipEventRecord(c->dev1, stream));
-    HIP_TRY(hipEventSynchronize(c->dev1));
     float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->dev0, c->dev1));
+    if (int rc = c->direct.end(stream, &ms)) return rc;
     stats->n = n;
     stats->kernel_ms = ms;
     if (count) {
         unsigned long long h[rtxd::DIRECT_COUNTER_SLOTS] = {0};
-        HIP_TRY(hipMemcpy(h, c->direct_counters.ptr, sizeof(h), hipMemcpyDeviceToHost));
+        if (int rc = c->direct.read(h, rtxd::DIRECT_COUNTER_SLOTS)) return rc;
         stats->sampled = h[rtxd::DIRECT_SAMPLED];
         stats->visible = h[rtxd::DIRECT_VISIBLE];
         stats->rng_draws = h[rtxd::DIRECT_RNG_DRAWS];
@@ -204,26 +162,17 @@ int rtx_direct(rtx_scene* s, uint64_t seed, const rtx_hit* hits, const rtx_path_
         if (stats) std::memset(stats, 0, sizeof(*stats));
         return RTX_OK;
     }
-    DeviceBuffer d_hits, d_keys, d_out;
-    rtx_direct_stats local;
-    int rc = RTX_OK;
     const size_t N = (size_t)n;
-    hipError_t e = d_hits.reserve(N * sizeof(rtx_hit));
-    if (e == hipSuccess) e = d_keys.reserve(N * sizeof(rtx_path_key));
-    if (e == hipSuccess) e = d_out.reserve(N * sizeof(rtx_direct_sample));
-    if (e == hipSuccess) e = hipMemcpy(d_hits.ptr, hits, N * sizeof(rtx_hit), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_keys.ptr, keys, N * sizeof(rtx_path_key), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        // (with stats: it returns after the kernels; without the caller's, the timed kernel)
-        rc = rtx_direct_device(s, seed, d_hits.as<rtx_hit>(), d_keys.as<rtx_path_key>(), n, d_out.as<rtx_direct_sample>(),
-                               stats ? flags : flags & ~RTX_DIRECT_COUNTERS, nullptr, &local);
-        if (rc == RTX_OK) e = hipMemcpy(out, d_out.ptr, N * sizeof(rtx_direct_sample), hipMemcpyDeviceToHost);
-    }
-    d_hits.release();
-    d_keys.release();
-    d_out.release();
-    if (rc != RTX_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "rtx_direct's buffers");
+    rtxd::Staging st({{hits, N * sizeof(rtx_hit), rtxd::Stage::in},
+                      {keys, N * sizeof(rtx_path_key), rtxd::Stage::in},
+                      {out, N * sizeof(rtx_direct_sample), rtxd::Stage::out}});
+    rtx_direct_stats local;
+    // (with stats: the device entry returns after the kernels; without the caller's, the timed kernel)
+    if (int rc = run_staged(st, "rtx_direct's buffers", [&] {
+            return rtx_direct_device(s, seed, st.dev<rtx_hit>(0), st.dev<rtx_path_key>(1), n, st.dev<rtx_direct_sample>(2),
+                                     stats ? flags : flags & ~RTX_DIRECT_COUNTERS, nullptr, &local);
+        }))
+        return rc;
     if (stats) *stats = local;
     return RTX_OK;
 }

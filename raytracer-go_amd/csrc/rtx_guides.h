@@ -6,20 +6,14 @@
 #include <stdint.h>
 
 #include "../../include/rtx.h"
+#include "rtx_walk.h"
 
 namespace rtxd {
 // One launch: the guides of the region's width * rows pixels (at most 2^32 - 1) over samples [k0, k0 + kn), kn >= 1.
 struct GuideParams {
-    rtx_camera cam;
-    uint64_t seed;
-    uint32_t x0, y0, width, rows, rank, world, stripe_log2;
-    uint32_t k0, kn;
+    Shard shard;
+    WalkScene scene;        // a trace layout
     uint32_t tile_w_log2;   // a wave's 64 pixels: 2^tile_w_log2 wide (3: 8 x 8, 6: 64 x 1)
-    const float4* entries;  // a trace layout (rtx_layout.h), as TraceParams'
-    uint32_t n_entries;
-    uint32_t n_quads;
-    uint32_t start;
-    uint32_t prim_end;
     uint32_t refill;        // folded-and-waiting lanes at which a wave folds and hands out the next samples (1..64)
     uint32_t prim_batch;    // primitive tests wait for this many lanes (trav_step_batched)
     uint32_t want_uv;       // the scene has an image texture: sphere hits need (u, v)

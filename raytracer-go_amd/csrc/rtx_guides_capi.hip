@@ -19,18 +19,13 @@ int check_guides(const rtx_scene* s, const rtx_camera* cam, const rtx_region* re
     if (int rc = check_camera(cam)) return rc;
     if (int rc = check_region(cam, region)) return rc;
     if (count == 0) return fail(RTX_ERR_INVALID_ARG, "guides over 0 samples (a mean over nothing)");
-    if ((uint64_t)first_sample + count > 0xFFFFFFFFull)
-        return fail(RTX_ERR_INVALID_ARG, "samples %u + %u pass 2^32 - 1 (the RNG's sample word is 32-bit)", first_sample, count);
+    if (int rc = check_sample_range(first_sample, count)) return rc;
     const uint64_t P = (uint64_t)region_rows(region) * region->width;
     if (P == 0) return RTX_OK;
     if (!guides) return fail(RTX_ERR_INVALID_ARG, "NULL argument");
     if (device && ((uintptr_t)guides & 15u)) return fail(RTX_ERR_INVALID_ARG, "guides must be aligned to 16 B");
     *pixels = P;
     return RTX_OK;
-}
-
-int hip_fail(hipError_t e, const char* what) {
-    return fail(e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
 
 bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
@@ -76,31 +71,15 @@ namespace rtxh {
 
 int guides_locked(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const rtx_region* region, uint32_t first_sample,
                   uint32_t count, rtx_guide* d_guides, hipStream_t stream, rtx_guide_stats* stats) {
-    int cur = 0;
-    HIP_TRY(hipGetDevice(&cur));
-    const auto it = s->copies.find(cur);
-    if (it == s->copies.end()) return fail(RTX_ERR_INVALID_ARG, "the scene has no copy on the current device %d", cur);
-    DeviceCopy* c = it->second.get();
+    DeviceCopy* c = nullptr;
+    if (int rc = current_copy(s, &c)) return rc;
     const DeviceLayout* lay = nullptr;
-    if (int rc = ensure_trace(s, c, rtx_camera_octant(cam), &lay)) return rc;  // (and the events a timed call uses)
+    // (and the trace's probe: a timed call borrows its events, the guides having no counters of their own)
+    if (int rc = ensure_trace(s, c, rtx_camera_octant(cam), &lay)) return rc;
     rtxd::GuideParams p;
     std::memset(&p, 0, sizeof(p));
-    p.cam = *cam;
-    p.seed = seed;
-    p.x0 = region->x0;
-    p.y0 = region->y0;
-    p.width = region->width;
-    p.rows = region_rows(region);
-    p.rank = region->rank;
-    p.world = region->world;
-    p.stripe_log2 = region->stripe > 1u ? (uint32_t)(31 - __builtin_clz(region->stripe)) : 0u;
-    p.k0 = first_sample;
-    p.kn = count;
-    p.entries = lay->entries.as<const float4>();
-    p.n_entries = lay->n_entries;
-    p.n_quads = (uint32_t)(s->quadtab.size() / 16);
-    p.start = lay->start;
-    p.prim_end = lay->prim_end;
+    p.shard = shard_of(cam, seed, region, first_sample, count);
+    p.scene = walk_scene(s, lay);
     p.want_uv = s->has_image ? 1u : 0u;
     p.materials = c->materials.as<const rtx_material>();
     p.textures = c->textures.as<const rtx_texture>();
@@ -113,15 +92,12 @@ int guides_locked(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const rtx_
     p.tile_w_log2 = env_knob("RTX_GUIDES_TILE_W_LOG2", 3, 0, 6);
     p.refill = env_knob("RTX_GUIDES_REFILL", 64, 1, 64);
     p.prim_batch = env_knob("RTX_GUIDES_PRIM_BATCH", 16, 1, 65);
-    if (stats) HIP_TRY(hipEventRecord(c->tev0, stream));
-    if (const hipError_t e = rtxd::launch_guides(p, s->has_noise, stream))
-        return fail(e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP, "guides launch failed: %s", hipGetErrorString(e));
+    if (int rc = c->trace.begin(false, stats != nullptr, stream)) return rc;
+    if (const hipError_t e = rtxd::launch_guides(p, s->has_noise, stream)) return hip_fail(e, "guides launch failed");
     if (!stats) return RTX_OK;
-    HIP_TRY(hipEventRecord(c->tev1, stream));
-    HIP_TRY(hipEventSynchronize(c->tev1));
     float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->tev0, c->tev1));
-    stats->rays = (uint64_t)p.width * p.rows * count;
+    if (int rc = c->trace.end(stream, &ms)) return rc;
+    stats->rays = (uint64_t)p.shard.width * p.shard.rows * count;
     stats->kernel_ms = ms;
     return RTX_OK;
 }
@@ -148,19 +124,13 @@ int rtx_guides(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const rtx_reg
     if (int rc = check_guides(s, cam, region, first_sample, count, guides, false, &pixels)) return rc;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (pixels == 0) return RTX_OK;
-    DeviceBuffer d;
-    const size_t bytes = (size_t)pixels * sizeof(rtx_guide);
-    hipError_t e = d.reserve(bytes);
-    int rc = RTX_OK;
-    if (e == hipSuccess) {
-        rtx_guide_stats local;
-        rc = rtx_guides_device(s, cam, seed, region, first_sample, count, d.as<rtx_guide>(), nullptr, &local);
-        if (rc == RTX_OK) e = hipMemcpy(guides, d.ptr, bytes, hipMemcpyDeviceToHost);
-        if (rc == RTX_OK && stats) *stats = local;
-    }
-    d.release();
-    if (rc != RTX_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "rtx_guides' buffer");
+    rtxd::Staging st({{guides, (size_t)pixels * sizeof(rtx_guide), rtxd::Stage::out}});
+    rtx_guide_stats local;
+    if (int rc = run_staged(st, "rtx_guides' buffer", [&] {
+            return rtx_guides_device(s, cam, seed, region, first_sample, count, st.dev<rtx_guide>(0), nullptr, &local);
+        }))
+        return rc;
+    if (stats) *stats = local;
     return RTX_OK;
 }
 
@@ -193,31 +163,17 @@ int rtx_denoise(const float* rgb, const float* var, const rtx_guide* guides, uin
     if (P == 0) return RTX_OK;
     if (P > 0x7FFFFFFFull) return fail(RTX_ERR_INVALID_ARG, "image too large for the filter");
     if (!rgb || !var || !guides || !out_rgb) return fail(RTX_ERR_INVALID_ARG, "NULL argument");
-    DeviceBuffer d_rgb, d_var, d_guides, d_out, d_work;
     const size_t img = (size_t)P * 3 * sizeof(float), gb = (size_t)P * sizeof(rtx_guide);
     const uint64_t wb = rtx_denoise_workspace_bytes(width, rows);
-    int rc = RTX_OK;
-    hipError_t e = d_rgb.reserve(img);
-    if (e == hipSuccess) e = d_var.reserve(img);
-    if (e == hipSuccess) e = d_guides.reserve(gb);
-    if (e == hipSuccess) e = d_out.reserve(img);
-    if (e == hipSuccess) e = d_work.reserve((size_t)wb);
-    if (e == hipSuccess) e = hipMemcpy(d_rgb.ptr, rgb, img, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_var.ptr, var, img, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_guides.ptr, guides, gb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = rtx_denoise_device(d_rgb.as<float>(), d_var.as<float>(), d_guides.as<rtx_guide>(), width, rows, params,
-                                d_out.as<float>(), d_work.ptr, wb, nullptr);
-        if (rc == RTX_OK) e = hipMemcpy(out_rgb, d_out.ptr, img, hipMemcpyDeviceToHost);  // (blocking: after the kernels)
-    }
-    d_rgb.release();
-    d_var.release();
-    d_guides.release();
-    d_out.release();
-    d_work.release();
-    if (rc != RTX_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "rtx_denoise's buffers");
-    return RTX_OK;
+    rtxd::Staging st({{rgb, img, rtxd::Stage::in},
+                      {var, img, rtxd::Stage::in},
+                      {guides, gb, rtxd::Stage::in},
+                      {out_rgb, img, rtxd::Stage::out},
+                      {nullptr, (size_t)wb, rtxd::Stage::scratch}});
+    return run_staged(st, "rtx_denoise's buffers", [&] {
+        return rtx_denoise_device(st.dev<float>(0), st.dev<float>(1), st.dev<rtx_guide>(2), width, rows, params, st.dev<float>(3),
+                                  st.dev<void>(4), wb, nullptr);
+    });
 }
 
 }  // extern "C"

@@ -10,11 +10,16 @@
 //                      camera rays and material scatter for a batch; rtx_guides_capi.hip: guide images and the
 //                      preview filter; rtx_direct_capi.hip: light samples and shadow rays for a batch;
 //                      rtx_capi.hip: scene create / destroy
+//   rtx_batch.hip      what the batch entry points (trace, shade, guides, direct) share: the scene's copy on the
+//                      current device, a feature's counters and events (Probe), the argument checks, the shard and
+//                      walk parameters of a launch
 //
 // A unit that defines RTX_HOST_ONLY before including this header sees the first half only, which names no HIP type:
 // it compiles with the plain host compiler and links without the runtime (tests/test_pack_layout.py).
 #pragma once
+#include <algorithm>
 #include <cstdint>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -117,6 +122,7 @@ PackedLayout pack_layout(const std::vector<rtx_entry>& E, const std::vector<doub
 #include "rtx_device.h"
 #include "rtx_devmem.h"
 #include "rtx_kernel.h"
+#include "rtx_walk.h"
 
 #define HIP_TRY(expr)                                                                             \
     do {                                                                                          \
@@ -137,6 +143,22 @@ struct DeviceLayout {
     uint32_t hot = 0, start = 0, prim_end = 0, n_entries = 0;  // PackedLayout's
 };
 
+// A feature's counters and events on a scene's copy, made on first use: its own, so that a counting or timed call
+// changes nobody else's stats.  Every method wants the copy's device current and returns an RTX_* code.
+struct Probe {
+    DeviceBuffer counters;  // `slots` x u64
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+
+    int ensure(uint32_t slots);
+    // Before the launches on `st`: count zeroes the counters, timed records ev0.
+    int begin(bool count, bool timed, hipStream_t st);
+    // After them (a timed call): records ev1, waits for it; *ms: from ev0 to ev1.
+    int end(hipStream_t st, float* ms);
+    int read(unsigned long long* h, uint32_t n);  // the first n counters, after end()
+    void release();
+    unsigned long long* slots() const { return counters.as<unsigned long long>(); }
+};
+
 struct DeviceCopy {
     int device = -1;
     DeviceLayout lay[16];  // [0, 8): the walk of each camera octant; [8, 16): the near walks of a tiered scene
@@ -150,16 +172,9 @@ struct DeviceCopy {
     // scene's tree for each hinted octant; a scene that keeps the caller's tree has trace_lay[0] alone.
     DeviceLayout trace_lay[8];
     DeviceBuffer rank_sphere;  // rank word of a sphere entry -> the caller's sphere index (first trace)
-    DeviceBuffer trace_counters;
-    hipEvent_t tev0 = nullptr, tev1 = nullptr;
-    // Path building blocks (rtx_shade_device): counters and events of their own (first shade).
-    DeviceBuffer shade_counters;
-    hipEvent_t sev0 = nullptr, sev1 = nullptr;
-    // Direct light sampling (rtx_direct_device): the emitter records, counters and events of their
-    // own (first call).
-    DeviceBuffer lights;
-    DeviceBuffer direct_counters;
-    hipEvent_t dev0 = nullptr, dev1 = nullptr;
+    DeviceBuffer lights;       // direct light sampling: the emitter records (first call)
+    // ray queries (and the guide images' timing), path building blocks, direct light sampling
+    Probe trace, shade, direct;
 
     unsigned long long* slot(uint32_t k) const { return counters.as<unsigned long long>() + k; }
     // a counter slot's low word, for the three the kernels claim from
@@ -244,9 +259,44 @@ int render_region_locked(rtx_scene* s, const rtx_camera* cam, uint64_t seed, con
 int ppm_to_host(int rc, const float* rgb, uint32_t W, uint32_t H, char* text, hipStream_t st, char* out_text,
                 uint64_t capacity, uint64_t* out_len);
 
+// ---- rtx_batch.hip -------------------------------------------------------------------------------------------
+int hip_fail(hipError_t e, const char* what);  // fail(RTX_ERR_OOM or RTX_ERR_HIP, "<what>: <HIP's text>")
+// The scene's copy on the current device (s->mu held); *device: that device.
+int current_copy(rtx_scene* s, DeviceCopy** out, int* device = nullptr);
+// The checks of a batch entry that need no device: the scene, the flags against `allowed`, then, unless n == 0
+// (*empty: nothing to do), the record arrays `args`: not NULL, aligned to 16 B, n * record_bytes within size_t.
+struct BatchArg {
+    const void* ptr;
+    const char* name;
+};
+int check_batch(const rtx_scene* s, uint32_t flags, uint32_t allowed, const char* feature, uint64_t n, size_t record_bytes,
+                std::initializer_list<BatchArg> args, bool* empty);
+// Samples [first, first + count) within the RNG's 32-bit sample word.
+int check_sample_range(uint32_t first, uint32_t count);
+// The launch parameters of a region's shard over samples [first, first + count), and of a trace layout.
+rtxd::Shard shard_of(const rtx_camera* cam, uint64_t seed, const rtx_region* region, uint32_t first, uint32_t count);
+rtxd::WalkScene walk_scene(const rtx_scene* s, const DeviceLayout* lay);
+// fn(offset, count) for [0, n) cut into launches of at most per_launch; stops at the first code that is not RTX_OK.
+template <class F>
+int for_launches(uint64_t n, uint64_t per_launch, F&& fn) {
+    for (uint64_t off = 0; off < n; off += per_launch)
+        if (int rc = fn(off, (uint32_t)std::min<uint64_t>(per_launch, n - off))) return rc;
+    return RTX_OK;
+}
+
+// A host-pointer entry through its Staging (rtx_devmem.h): call()'s code wins, else a failed reserve or copy is
+// RTX_ERR_OOM / RTX_ERR_HIP with `what` ("<entry>'s buffers").
+template <class S, class F>
+int run_staged(S& st, const char* what, F&& call) {
+    int rc = RTX_OK;
+    const hipError_t e = st.run(call, &rc);
+    if (rc != RTX_OK) return rc;
+    return e == hipSuccess ? RTX_OK : hip_fail(e, what);
+}
+
 // ---- rtx_trace_capi.hip --------------------------------------------------------------------------------------
-// What a trace on copy c needs beside the scene (s->mu held, current device = c's), made on first use; *out: the
-// trace layout for the hinted octant.
+// What a trace on copy c needs beside the scene (s->mu held, current device = c's), made on first use (c->trace's
+// counters and events among it); *out: the trace layout for the hinted octant.
 int ensure_trace(rtx_scene* s, DeviceCopy* c, uint32_t oct, const DeviceLayout** out);
 
 // ---- rtx_guides_capi.hip -------------------------------------------------------------------------------------

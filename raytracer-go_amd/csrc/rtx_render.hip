@@ -70,10 +70,9 @@ void free_copy(DeviceCopy& c) {
     (void)hipDeviceSynchronize();  // no render of this copy still running
     for (DeviceLayout& l : c.lay) l.entries.release();
     for (DeviceLayout& l : c.trace_lay) l.entries.release();
-    for (DeviceBuffer* b : {&c.rank_sphere, &c.trace_counters, &c.shade_counters, &c.lights, &c.direct_counters, &c.materials,
-                            &c.textures, &c.texels, &c.counters})
-        b->release();
-    for (hipEvent_t ev : {c.dev0, c.dev1, c.sev0, c.sev1, c.tev0, c.tev1, c.ev0, c.ev1})
+    for (DeviceBuffer* b : {&c.rank_sphere, &c.lights, &c.materials, &c.textures, &c.texels, &c.counters}) b->release();
+    for (Probe* p : {&c.trace, &c.shade, &c.direct}) p->release();
+    for (hipEvent_t ev : {c.ev0, c.ev1})
         if (ev) (void)hipEventDestroy(ev);
 }
 
@@ -350,7 +349,7 @@ int enqueue_on(rtx_scene* s, DeviceCopy* c, const rtx_camera* cam, uint64_t seed
     if (const hipError_t e = *tiered ? rtxd::launch_render(pn, flags, stream, &p, pass)
                                      : rtxd::launch_render(p, flags, stream, nullptr, pass)) {
         scr->redo_zero = 0;  // a chunk may have stopped between setting redo bits and clearing them
-        return fail(e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP, "render launch failed: %s", hipGetErrorString(e));
+        return hip_fail(e, "render launch failed");
     }
     if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
     HIP_TRY(hipEventRecord(scr->last, stream));

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/rtx.h"
+#include "rtx_walk.h"
 
 namespace rtxd {
 // Device counters of a counting shade, in memory of the scene copy's own (never the render's or the trace's).
@@ -34,10 +35,7 @@ hipError_t launch_shade(const ShadeParams& p, bool count, bool noise, hipStream_
 // second dimension); record (k - k0) * P + i * width + xx goes to rays[...] (and keys[...] when keys != nullptr).
 constexpr uint32_t CAMERA_LAUNCH_SAMPLES = 65535u;
 struct CameraRayParams {
-    rtx_camera cam;
-    uint64_t seed;
-    uint32_t x0, y0, width, rows, rank, world, stripe_log2;
-    uint32_t k0, kn;
+    Shard shard;
     rtx_ray* rays;
     rtx_path_key* keys;
 };

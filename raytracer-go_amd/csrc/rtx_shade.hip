@@ -18,7 +18,7 @@
 // return the same bits for every lane the short form admits, and the ballot only sees active lanes, so a vote taken by
 // a part of the wave (the lanes of one material, the lanes still rejecting in rand_unit_on_sphere) picks a form that
 // is right for each of them.  The render's shade() takes the same votes inside the same branches.  Unit(r.dir) of
-// Metal and Dielectric is computed by the whole wave and selected per lane, as write_hit does (rtx_trace.hip).
+// Metal and Dielectric is computed by the whole wave and selected per lane, as hit_record does (rtx_walk.h).
 #include "rtx_shade.h"
 
 #include "rtx_device.h"
@@ -141,18 +141,19 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_hits(ShadeParams p) {
 
 // GetRay for pixel blockIdx.x * SHADE_BLOCK + lane of the region's shard and sample k0 + blockIdx.y.
 __global__ __launch_bounds__(SHADE_BLOCK) void camera_rays(CameraRayParams p) {
-    const uint64_t P = (uint64_t)p.width * p.rows;  // at most 2^32 - 1 (check_camera)
+    const Shard& sh = p.shard;
+    const uint64_t P = (uint64_t)sh.width * sh.rows;  // at most 2^32 - 1 (check_camera)
     const uint64_t i = (uint64_t)blockIdx.x * SHADE_BLOCK + threadIdx.x;
     const bool live = i < P;
     const uint32_t j = (uint32_t)(live ? i : P - 1u);
-    const uint32_t lr = j / p.width, xx = j - lr * p.width;
-    const uint32_t x = p.x0 + xx, y = p.y0 + region_row(lr, p.rank, p.world, p.stripe_log2);
-    const uint32_t k = p.k0 + blockIdx.y;
-    const uint32_t pixel = y * p.cam.image_width + x;  // the GLOBAL pixel index: the RNG's counter word
-    const PathRng rng{(uint32_t)p.seed, (uint32_t)(p.seed >> 32), pixel, k};
+    const uint32_t lr = j / sh.width, xx = j - lr * sh.width;
+    const uint32_t x = sh.x0 + xx, y = sh.y0 + region_row(lr, sh.rank, sh.world, sh.stripe_log2);
+    const uint32_t k = sh.k0 + blockIdx.y;
+    const uint32_t pixel = y * sh.cam.image_width + x;  // the GLOBAL pixel index: the RNG's counter word
+    const PathRng rng{(uint32_t)sh.seed, (uint32_t)(sh.seed >> 32), pixel, k};
     uint32_t draws = 0;
     // event 0: block (0, 0) gives dx, dy and the first disk pair; the disk's rejection loop always runs
-    const Ray r = camera_ray<false>(p.cam, pixel_base(p.cam, x, y), rng, rng.block(0, 0), draws);
+    const Ray r = camera_ray<false>(sh.cam, pixel_base(sh.cam, x, y), rng, rng.block(0, 0), draws);
     if (live) {  // 32 B (+ 16 B): two (+ one) dwordx4 stores
         const uint64_t rec = (uint64_t)blockIdx.y * P + i;
         float4* o = reinterpret_cast<float4*>(p.rays + rec);
@@ -181,11 +182,12 @@ hipError_t launch_shade(const ShadeParams& p, bool count, bool noise, hipStream_
 }
 
 hipError_t launch_camera_rays(const CameraRayParams& p, hipStream_t stream) {
-    const uint64_t P = (uint64_t)p.width * p.rows;
-    if (P == 0 || p.kn == 0) return hipSuccess;
-    if (P > 0xFFFFFFFFull || p.kn > CAMERA_LAUNCH_SAMPLES || !p.rays || p.world == 0 || p.rank >= p.world)
+    const Shard& sh = p.shard;
+    const uint64_t P = (uint64_t)sh.width * sh.rows;
+    if (P == 0 || sh.kn == 0) return hipSuccess;
+    if (P > 0xFFFFFFFFull || sh.kn > CAMERA_LAUNCH_SAMPLES || !p.rays || sh.world == 0 || sh.rank >= sh.world)
         return hipErrorInvalidValue;
-    const dim3 grid((uint32_t)((P + SHADE_BLOCK - 1) / SHADE_BLOCK), p.kn), block(SHADE_BLOCK);
+    const dim3 grid((uint32_t)((P + SHADE_BLOCK - 1) / SHADE_BLOCK), sh.kn), block(SHADE_BLOCK);
     hipLaunchKernelGGL(camera_rays, grid, block, 0, stream, p);
     return hipGetLastError();
 }

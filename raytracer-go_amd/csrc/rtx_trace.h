@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/rtx.h"
+#include "rtx_walk.h"
 
 namespace rtxd {
 // Device counters of a counting trace, in memory of the scene copy's own (never the render's).
@@ -13,11 +14,7 @@ constexpr uint32_t TRACE_HITS = 0u, TRACE_NODE_VISITS = 1u, TRACE_PRIM_TESTS = 2
 // One launch: rays [0, n) of `rays` into `hits`, n <= TRACE_LAUNCH_MAX (ray indices are 32-bit).
 constexpr uint64_t TRACE_LAUNCH_MAX = 1ull << 30;
 struct TraceParams {
-    const float4* entries;  // a trace layout (rtx_layout.h): n_entries + 1 'a' halves, as many 'b', 4 * n_quads
-    uint32_t n_entries;
-    uint32_t n_quads;
-    uint32_t start;     // walk position of the root
-    uint32_t prim_end;  // scene in the LDS copy: its primitives are stored below this position
+    WalkScene scene;  // a trace layout
     const uint32_t* rank_sphere;  // rank word of a sphere entry (its 'b'.y) -> index into the caller's sphere table
     const rtx_ray* rays;
     rtx_hit* hits;

@@ -15,21 +15,13 @@
 // rays are begun and hit records computed on all 64 lanes, and only the selects and stores are per lane.
 #include "rtx_trace.h"
 
-#include "rtx_device.h"
+#include "rtx_walk.h"
 
 namespace rtxd {
 namespace {
 
-constexpr int TRACE_WAVES = 8;            // waves per workgroup (one LDS copy of the scene each)
-constexpr uint32_t TRACE_STEPS = 4;       // walk steps between two votes on the parked lanes
 constexpr uint32_t TRACE_NO_RAY = 0xFFFFFFFFu;
 constexpr uint32_t TRACE_LDS_MAX = 64 * 1024;
-
-// LDS bytes of the fixed layout without materials (scene_ref_fixed with none): the 'a' halves from byte 0, the 'b'
-// halves from LDS_B, then the quad table.
-__host__ __device__ inline uint32_t trace_lds_bytes(uint32_t n_entries, uint32_t n_quads) {
-    return LDS_B + (n_entries + 1) * 16 + n_quads * 64;
-}
 
 struct Query {
     Ray r;
@@ -37,53 +29,18 @@ struct Query {
     uint32_t index;  // the lane's ray, TRACE_NO_RAY when it has none
 };
 
-// The rtx_hit of a lane's finished walk, computed by every lane (unit's votes) and stored where `fin`:
-// NewHitInfo (hittables.go:22-37) of what Sphere.Hit (:118-129) or Quad.Hit (:180-190) hand it, as shade() forms
-// them (rtx_device.h).  A miss: t = +inf, prim = RTX_HIT_NONE, the rest 0.
+// The rtx_hit of a lane's finished walk: hit_record (rtx_walk.h) by every lane, stored where `fin`.  A miss:
+// t = +inf, prim = RTX_HIT_NONE, the rest 0.
 template <bool QUADS>
 __device__ __forceinline__ void write_hit(const TraceParams& p, const SceneRef E, const Trav& t, const Query& q,
                                           const bool fin) {
-    const bool hit = t.hit >= 0;
-    const uint32_t e = hit ? (uint32_t)t.hit : 0u;  // (a miss reads entry 0 and drops it)
-    const float4 sa = E.a[e];
-    const float4 sb = E.b[e];
-    const bool quad = QUADS && hit && __float_as_int(sb.w) == RTX_E_QUAD;
-    const V3 pt = add(scale(q.r.d, t.closest), q.r.o);                            // ray.go:25-30
-    const V3 ns = unit(scale(sub(pt, v3(sa.x, sa.y, sa.z)), sa.w));               // hittables.go:119-120
-    V3 n = ns;
-    uint32_t prim = 0xFFFFFFFFu, mi = 0u;
-    float u = 0.0f, v = 0.0f;
-    const bool want_uv = (p.flags & RTX_TRACE_UV) != 0u;
-    if (quad) {
-        const uint32_t qk = (uint32_t)__float_as_int(sb.x), qi = 4u * qk;
-        const float4 q0 = E.q[qi];
-        mi = (uint32_t)__float_as_int(q0.w);
-        n = v3(sa.x, sa.y, sa.z);                                                 // q.normal
-        prim = (RTX_PRIM_QUAD << 28) | qk;
-        if (want_uv) {  // (alpha, beta) as quad_test formed them (hittables.go:181-183)
-            const float4 q1 = E.q[qi + 1], q2 = E.q[qi + 2], q3 = E.q[qi + 3];
-            const V3 php = sub(pt, v3(q0.x, q0.y, q0.z));
-            const V3 w = v3(q3.x, q3.y, q3.z);
-            u = dot(w, cross(php, v3(q2.x, q2.y, q2.z)));
-            v = dot(w, cross(v3(q1.x, q1.y, q1.z), php));
-        }
-    } else if (hit) {
-        mi = RTX_DEV_SPHERE_MATERIAL(__float_as_int(sb.w));
-        prim = (RTX_PRIM_SPHERE << 28) | p.rank_sphere[__float_as_uint(sb.y)];
-        if (want_uv) {                                                            // hittables.go:122-126
-            const UV uv = sphere_uv(n.x, n.y, n.z);
-            u = uv.u;
-            v = uv.v;
-        }
-    }
-    const bool front = dot(q.r.d, n) < 0.0f;                                      // hittables.go:23
-    if (!front) n = scale(n, -1.0f);                                              // :24-26
+    const HitRecord h = hit_record<QUADS, true>(E, t, q.r, (p.flags & RTX_TRACE_UV) != 0u, p.rank_sphere);
     if (fin) {
         float4 h0, h1, h2;
-        if (hit) {
-            h0 = make_float4(t.closest, __uint_as_float(prim), __uint_as_float(mi), __uint_as_float(front ? 1u : 0u));
-            h1 = make_float4(pt.x, pt.y, pt.z, u);
-            h2 = make_float4(n.x, n.y, n.z, v);
+        if (h.hit) {
+            h0 = make_float4(t.closest, __uint_as_float(h.prim), __uint_as_float(h.mi), __uint_as_float(h.front ? 1u : 0u));
+            h1 = make_float4(h.pt.x, h.pt.y, h.pt.z, h.u);
+            h2 = make_float4(h.n.x, h.n.y, h.n.z, h.v);
         } else {
             h0 = make_float4(__builtin_inff(), __uint_as_float(0xFFFFFFFFu), 0.0f, 0.0f);
             h1 = h2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -99,28 +56,13 @@ __device__ __forceinline__ void write_hit(const TraceParams& p, const SceneRef E
 // scene in the workgroup's LDS copy (scene_ref_fixed), else read from HBM.  ANY: RTX_TRACE_ANY, a lane parks at
 // its first accepted primitive.
 template <bool COUNT, bool QUADS, bool FIXED, bool ANY>
-__global__ __launch_bounds__(64 * TRACE_WAVES) void trace_rays(TraceParams p) {
+__global__ __launch_bounds__(64 * WALK_WAVES) void trace_rays(TraceParams p) {
     extern __shared__ float4 lds_entries[];
-    SceneRef E;
-    if constexpr (FIXED) {
-        // scene_ref_fixed: the walk addresses LDS directly, so the copy must start at 0
-        if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) float4*)lds_entries != 0u) __builtin_trap();
-        const uint32_t m = p.n_entries + 1, nq4 = 4 * p.n_quads;
-        for (uint32_t i = threadIdx.x; i < m; i += 64 * TRACE_WAVES) {
-            lds_entries[i] = p.entries[i];
-            lds_entries[LDS_B / 16 + i] = p.entries[m + i];
-        }
-        for (uint32_t i = threadIdx.x; i < nq4; i += 64 * TRACE_WAVES) lds_entries[LDS_B / 16 + m + i] = p.entries[2 * m + i];
-        __syncthreads();
-        E = scene_ref_fixed(lds_entries, p.n_entries, p.n_quads, 0u, 0u);
-        E.prim_end = p.prim_end;
-    } else {
-        E = scene_ref(p.entries, p.n_entries, nullptr);
-    }
-    const uint32_t end = 16 * p.n_entries;  // the sentinel's position
+    const SceneRef E = stage_scene<WALK_WAVES, FIXED>(lds_entries, p.scene);
+    const uint32_t end = walk_end(p.scene);
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t below = (1ull << lane) - 1ull;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * TRACE_WAVES + (threadIdx.x >> 6));
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * WALK_WAVES + (threadIdx.x >> 6));
     const uint64_t first = (uint64_t)wave * p.range;
     if (first >= p.n) return;  // (the whole wave)
     uint32_t next = (uint32_t)first;
@@ -167,7 +109,7 @@ __global__ __launch_bounds__(64 * TRACE_WAVES) void trace_rays(TraceParams p) {
                 }
             }
             Trav nt;
-            trav_begin(nt, nq.r, p.start);  // (whole wave: its votes)
+            trav_begin(nt, nq.r, p.scene.start);  // (whole wave: its votes)
             // the fast step forms (med3 boxes, div_by roots) also need every accepted root normal: tmin >= 2^-126
             nt.safe = nt.safe && nq.tmin >= 0x1p-126f;
             nt.closest = tmax;  // the running bound starts at the ray's tmax
@@ -178,23 +120,7 @@ __global__ __launch_bounds__(64 * TRACE_WAVES) void trace_rays(TraceParams p) {
                 q.index = TRACE_NO_RAY;  // written above; stays on the sentinel
             }
         }
-        // TRACE_STEPS walk steps: the med3 / div_by forms when every walking lane's ray is safe (traverse_phase)
-        uint32_t idle = 0;
-        if (ballot(!t.safe && t.i < end) == 0) {
-#pragma unroll
-            for (uint32_t s = 0; s < TRACE_STEPS; ++s) {
-                trav_step_batched<COUNT, QUADS, FIXED, false, true>(t, q.r, E, cnt, end, p.prim_batch, idle,
-                                                                    V3{0.0f, 0.0f, 0.0f}, q.tmin);
-                if (ANY && t.hit >= 0) t.i = end;
-            }
-        } else {
-#pragma unroll
-            for (uint32_t s = 0; s < TRACE_STEPS; ++s) {
-                trav_step_batched<COUNT, QUADS, FIXED, false, false>(t, q.r, E, cnt, end, p.prim_batch, idle,
-                                                                     V3{0.0f, 0.0f, 0.0f}, q.tmin);
-                if (ANY && t.hit >= 0) t.i = end;
-            }
-        }
+        t = walk_steps<WALK_STEPS, COUNT, QUADS, FIXED>(t, q.r, E, cnt, end, p.prim_batch, q.tmin, ANY);
     }
     if (COUNT) {
         if (visits) atomicAdd(&p.counters[TRACE_NODE_VISITS], visits);
@@ -205,9 +131,9 @@ __global__ __launch_bounds__(64 * TRACE_WAVES) void trace_rays(TraceParams p) {
 
 template <bool COUNT, bool QUADS, bool FIXED>
 hipError_t launch_any(const TraceParams& p, hipStream_t stream) {
-    const size_t shmem = FIXED ? trace_lds_bytes(p.n_entries, p.n_quads) : 0;
+    const size_t shmem = FIXED ? walk_lds_bytes(p.scene.n_entries, p.scene.n_quads) : 0;
     const uint64_t waves = ((uint64_t)p.n + p.range - 1) / p.range;
-    const dim3 grid((uint32_t)((waves + TRACE_WAVES - 1) / TRACE_WAVES)), block(64 * TRACE_WAVES);
+    const dim3 grid((uint32_t)((waves + WALK_WAVES - 1) / WALK_WAVES)), block(64 * WALK_WAVES);
     if (p.flags & RTX_TRACE_ANY) hipLaunchKernelGGL((trace_rays<COUNT, QUADS, FIXED, true>), grid, block, shmem, stream, p);
     else hipLaunchKernelGGL((trace_rays<COUNT, QUADS, FIXED, false>), grid, block, shmem, stream, p);
     return hipGetLastError();
@@ -215,8 +141,8 @@ hipError_t launch_any(const TraceParams& p, hipStream_t stream) {
 
 template <bool COUNT>
 hipError_t launch_count(const TraceParams& p, hipStream_t stream) {
-    const bool fixed = trace_placement(p.n_entries, p.n_quads) == RTX_SCENE_IN_LDS;
-    if (p.n_quads) return fixed ? launch_any<COUNT, true, true>(p, stream) : launch_any<COUNT, true, false>(p, stream);
+    const bool fixed = trace_placement(p.scene.n_entries, p.scene.n_quads) == RTX_SCENE_IN_LDS;
+    if (p.scene.n_quads) return fixed ? launch_any<COUNT, true, true>(p, stream) : launch_any<COUNT, true, false>(p, stream);
     return fixed ? launch_any<COUNT, false, true>(p, stream) : launch_any<COUNT, false, false>(p, stream);
 }
 
@@ -224,7 +150,7 @@ hipError_t launch_count(const TraceParams& p, hipStream_t stream) {
 
 uint32_t trace_placement(uint32_t n_entries, uint32_t n_quads) {
     // as scene_placement (rtx_kernel.hip) without materials: the 'a' halves below LDS_B and all of it in 64 KB
-    return ((uint64_t)n_entries + 1) * 16 <= LDS_B && (uint64_t)trace_lds_bytes(n_entries, 0) + (uint64_t)n_quads * 64 <= TRACE_LDS_MAX
+    return ((uint64_t)n_entries + 1) * 16 <= LDS_B && (uint64_t)walk_lds_bytes(n_entries, 0) + (uint64_t)n_quads * 64 <= TRACE_LDS_MAX
                ? RTX_SCENE_IN_LDS
                : RTX_SCENE_IN_HBM;
 }
@@ -232,7 +158,7 @@ uint32_t trace_placement(uint32_t n_entries, uint32_t n_quads) {
 hipError_t launch_trace(const TraceParams& p, bool count, hipStream_t stream) {
     if (p.n == 0) return hipSuccess;
     if (p.n > TRACE_LAUNCH_MAX || p.range == 0 || p.range % 64u != 0 || p.refill == 0 || p.refill > 64u || !p.rays ||
-        !p.hits || !p.entries || !p.rank_sphere || (count && !p.counters))
+        !p.hits || !p.scene.entries || !p.rank_sphere || (count && !p.counters))
         return hipErrorInvalidValue;
     return count ? launch_count<true>(p, stream) : launch_count<false>(p, stream);
 }

@@ -14,17 +14,7 @@ constexpr uint32_t TRACE_FLAGS = RTX_TRACE_ANY | RTX_TRACE_UV | RTX_TRACE_COUNTE
 
 // The checks of both entries that need no device.  *empty: nothing to do (n == 0).
 int check_trace(const rtx_scene* s, const void* rays, uint64_t n, const void* hits, uint32_t flags, bool* empty) {
-    *empty = false;
-    if (!s) return fail(RTX_ERR_INVALID_ARG, "NULL scene");
-    if (flags & ~TRACE_FLAGS) return fail(RTX_ERR_INVALID_ARG, "unknown trace flags 0x%x", flags & ~TRACE_FLAGS);
-    if (n == 0) {
-        *empty = true;
-        return RTX_OK;
-    }
-    if (!rays || !hits) return fail(RTX_ERR_INVALID_ARG, "NULL argument");
-    if (((uintptr_t)rays | (uintptr_t)hits) & 15u) return fail(RTX_ERR_INVALID_ARG, "rays and hits must be aligned to 16 B");
-    if (n > (uint64_t)std::numeric_limits<size_t>::max() / sizeof(rtx_hit)) return fail(RTX_ERR_INVALID_ARG, "too many rays");
-    return RTX_OK;
+    return check_batch(s, flags, TRACE_FLAGS, "trace", n, sizeof(rtx_hit), {{rays, "rays"}, {hits, "hits"}}, empty);
 }
 
 }  // namespace
@@ -55,9 +45,7 @@ int ensure_trace(rtx_scene* s, DeviceCopy* c, uint32_t oct, const DeviceLayout**
             }
         }
     }
-    HIP_TRY(c->trace_counters.reserve(rtxd::TRACE_COUNTER_SLOTS * sizeof(unsigned long long)));
-    if (!c->tev0) HIP_TRY(hipEventCreate(&c->tev0));
-    if (!c->tev1) HIP_TRY(hipEventCreate(&c->tev1));
+    if (int rc = c->trace.ensure(rtxd::TRACE_COUNTER_SLOTS)) return rc;
     DeviceLayout& lay = c->trace_lay[s->rebuilt ? oct & 7u : 0u];
     if (!lay.entries.ptr) {
         std::vector<rtx_entry> full;
@@ -80,11 +68,8 @@ int rtx_trace_device(rtx_scene* s, const rtx_ray* d_rays, uint64_t n, rtx_hit* d
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (empty) return RTX_OK;
     std::lock_guard<std::mutex> lk(s->mu);
-    int cur = 0;
-    HIP_TRY(hipGetDevice(&cur));
-    const auto it = s->copies.find(cur);
-    if (it == s->copies.end()) return fail(RTX_ERR_INVALID_ARG, "the scene has no copy on the current device %d", cur);
-    DeviceCopy* c = it->second.get();
+    DeviceCopy* c = nullptr;
+    if (int rc = current_copy(s, &c)) return rc;
     const uint32_t oct = (flags >> 8) & 7u;
     const DeviceLayout* lay = nullptr;
     if (int rc = ensure_trace(s, c, oct, &lay)) return rc;
@@ -92,14 +77,10 @@ int rtx_trace_device(rtx_scene* s, const rtx_ray* d_rays, uint64_t n, rtx_hit* d
     const bool count = stats && (flags & RTX_TRACE_COUNTERS);
     rtxd::TraceParams p;
     std::memset(&p, 0, sizeof(p));
-    p.entries = lay->entries.as<const float4>();
-    p.n_entries = lay->n_entries;
-    p.n_quads = (uint32_t)(s->quadtab.size() / 16);
-    p.start = lay->start;
-    p.prim_end = lay->prim_end;
+    p.scene = walk_scene(s, lay);
     p.rank_sphere = c->rank_sphere.as<uint32_t>();
     p.flags = flags;
-    p.counters = c->trace_counters.as<unsigned long long>();
+    p.counters = c->trace.slots();
     // A/B knobs (read per call): rays per wave, the parked lanes at which a wave refills (64: whole blocks of 64
     // rays, the plain form; 48 measured -0.7 % on camera rays and +54 % on incoherent ones against it, DESIGN.md
     // §32), the lanes a primitive test waits for
@@ -108,27 +89,25 @@ int rtx_trace_device(rtx_scene* s, const rtx_ray* d_rays, uint64_t n, rtx_hit* d
     p.prim_batch = env_knob("RTX_TRACE_PRIM_BATCH", 16, 1, 65);
     // rays per launch (32-bit ray indices; RTX_TRACE_LAUNCH_RAYS: tests of the cut)
     const uint64_t per_launch = env_knob("RTX_TRACE_LAUNCH_RAYS", (long)rtxd::TRACE_LAUNCH_MAX, 64, (long)rtxd::TRACE_LAUNCH_MAX);
-    if (count) HIP_TRY(hipMemsetAsync(c->trace_counters.ptr, 0, c->trace_counters.bytes, stream));
-    if (stats) HIP_TRY(hipEventRecord(c->tev0, stream));
-    for (uint64_t off = 0; off < n; off += per_launch) {
-        p.rays = d_rays + off;
-        p.hits = d_hits + off;
-        p.n = (uint32_t)std::min<uint64_t>(per_launch, n - off);
-        if (const hipError_t e = rtxd::launch_trace(p, count, stream))
-            return fail(e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP, "trace launch failed: %s", hipGetErrorString(e));
-    }
+    if (int rc = c->trace.begin(count, stats != nullptr, stream)) return rc;
+    if (int rc = for_launches(n, per_launch, [&](uint64_t off, uint32_t m) {
+            p.rays = d_rays + off;
+            p.hits = d_hits + off;
+            p.n = m;
+            const hipError_t e = rtxd::launch_trace(p, count, stream);
+            return e == hipSuccess ? RTX_OK : hip_fail(e, "trace launch failed");
+        }))
+        return rc;
     if (!stats) return RTX_OK;
-    HIP_TRY(hipEventRecord(c->tev1, stream));
-    HIP_TRY(hipEventSynchronize(c->tev1));
     float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->tev0, c->tev1));
+    if (int rc = c->trace.end(stream, &ms)) return rc;
     stats->rays = n;
     stats->kernel_ms = ms;
     stats->walk_layout = s->rebuilt ? oct : RTX_LAYOUT_REFERENCE;
-    stats->scene_placement = rtxd::trace_placement(p.n_entries, p.n_quads);
+    stats->scene_placement = rtxd::trace_placement(p.scene.n_entries, p.scene.n_quads);
     if (count) {
         unsigned long long h[rtxd::TRACE_COUNTER_SLOTS] = {0};
-        HIP_TRY(hipMemcpy(h, c->trace_counters.ptr, sizeof(h), hipMemcpyDeviceToHost));
+        if (int rc = c->trace.read(h, rtxd::TRACE_COUNTER_SLOTS)) return rc;
         stats->hits = h[rtxd::TRACE_HITS];
         stats->node_visits = h[rtxd::TRACE_NODE_VISITS];
         stats->prim_tests = h[rtxd::TRACE_PRIM_TESTS];
@@ -144,23 +123,14 @@ int rtx_trace(rtx_scene* s, const rtx_ray* rays, uint64_t n, rtx_hit* hits, uint
         if (stats) std::memset(stats, 0, sizeof(*stats));
         return RTX_OK;
     }
-    DeviceBuffer d_rays, d_hits;
+    rtxd::Staging st({{rays, (size_t)n * sizeof(rtx_ray), rtxd::Stage::in}, {hits, (size_t)n * sizeof(rtx_hit), rtxd::Stage::out}});
     rtx_trace_stats local;
-    int rc = RTX_OK;
-    hipError_t e = d_rays.reserve((size_t)n * sizeof(rtx_ray));
-    if (e == hipSuccess) e = d_hits.reserve((size_t)n * sizeof(rtx_hit));
-    if (e == hipSuccess) e = hipMemcpy(d_rays.ptr, rays, (size_t)n * sizeof(rtx_ray), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        // (with stats: it returns after the kernels; without the caller's, the timed kernel)
-        rc = rtx_trace_device(s, d_rays.as<rtx_ray>(), n, d_hits.as<rtx_hit>(), stats ? flags : flags & ~RTX_TRACE_COUNTERS,
-                              nullptr, &local);
-        if (rc == RTX_OK) e = hipMemcpy(hits, d_hits.ptr, (size_t)n * sizeof(rtx_hit), hipMemcpyDeviceToHost);
-    }
-    d_rays.release();
-    d_hits.release();
-    if (rc != RTX_OK) return rc;
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP, "rtx_trace's buffers: %s", hipGetErrorString(e));
+    // (with stats: the device entry returns after the kernels; without the caller's, the timed kernel)
+    if (int rc = run_staged(st, "rtx_trace's buffers", [&] {
+            return rtx_trace_device(s, st.dev<rtx_ray>(0), n, st.dev<rtx_hit>(1), stats ? flags : flags & ~RTX_TRACE_COUNTERS,
+                                    nullptr, &local);
+        }))
+        return rc;
     if (stats) *stats = local;
     return RTX_OK;
 }

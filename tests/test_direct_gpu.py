@@ -296,6 +296,89 @@ def test_noise_textured_emitter_and_albedo(torch):
         dev.close()
 
 
+def memory_scene():
+    """One emitting quad, one emitting sphere, a Lambertian floor and a 32 x 32 grid of small Lambertian spheres under
+    a binary tree of its own: 3 + 1023 nodes + 1024 spheres = 2050 entries, the fewest of a square grid with
+    (entries + 1) * 16 B past the 32 KB of 'a' halves the LDS copy holds (2048 entries).  The grid floats between the
+    floor and the lights, so a good part of the floor's shadow rays is blocked."""
+    texs = [ds.solid(0.8, 0.7, 0.6), ds.solid(6, 5, 4), ds.solid(3, 4, 5), ds.solid(0.2, 0.5, 0.3)]
+    mats = [ds.material(ds.LAMB, 0), ds.material(ds.LIGHT, 1), ds.material(ds.LIGHT, 2), ds.material(ds.LAMB, 3)]
+    quads = [ds.quad((-4, 0, -4), (0, 0, 8), (8, 0, 0), 0),   # floor, normal +y
+             ds.quad((-1, 3, -1), (2, 0, 0), (0, 0, 2), 1)]   # light, normal -y
+    g, radius = 32, F32(0.05)
+    xz = (np.arange(g, dtype=F32) - F32((g - 1) / 2)) * F32(0.2)
+    centres = np.stack([np.repeat(xz, g), np.full(g * g, 0.9, F32), np.tile(xz, g)], axis=1).astype(F32)
+    spheres = [ds.sphere((2, 1.6, 0), 0.5, 2)] + [ds.sphere([float(v) for v in c], float(radius), 3) for c in centres]
+    nodes = []
+
+    def build(idx, axis):  # a median split, x and z in turn; the grid's sphere k is sphere 1 + k of the table
+        if len(idx) == 1:
+            return rtx.ref_prim(rtx.RTX_PRIM_SPHERE, 1 + int(idx[0]))
+        me = len(nodes)
+        nodes.append(rtx.BvhNode())
+        idx = idx[np.argsort(centres[idx, axis], kind="stable")]
+        left, right = build(idx[: len(idx) // 2], 2 - axis), build(idx[len(idx) // 2:], 2 - axis)
+        n = nodes[me]
+        n.bmin[:] = [float(v) for v in centres[idx].min(axis=0) - radius]
+        n.bmax[:] = [float(v) for v in centres[idx].max(axis=0) + radius]
+        n.left, n.right = left, right
+        return me
+
+    root = build(np.arange(g * g), 0)
+    roots = [rtx.ref_prim(rtx.RTX_PRIM_QUAD, 0), rtx.ref_prim(rtx.RTX_PRIM_QUAD, 1), rtx.ref_prim(rtx.RTX_PRIM_SPHERE, 0), root]
+    desc = ds.world(spheres, quads, mats, texs, roots=roots)
+    desc._keep["nodes"] = (rtx.BvhNode * len(nodes))(*nodes)
+    desc.contents.n_nodes, desc.contents.nodes = len(nodes), desc._keep["nodes"]
+    return desc, ds.five()[1]
+
+
+def test_a_scene_read_from_memory(torch):
+    """direct_lights and direct_paths on a layout read from HBM (the FIXED = false instantiations), a 24 x 13 window:
+    312 records, a partial last wave.  The block equals direct_ref bit for bit, VISIBLE equals the any-hit trace, and
+    add_direct of 3 samples resolves bit-equal to the composed blocks."""
+    desc, cam = memory_scene()
+    region = rtx.Region(20, 12, 24, 13, 0, 1)
+    dev = rtx.DeviceScene(desc, reference_bvh=True, every_box=True)
+    try:
+        P = rtx.region_rows(region) * region.width
+        assert P == 312
+        d_rays = torch.empty((P, 8), dtype=torch.float32, device="cuda")
+        d_keys = torch.empty((P, 4), dtype=torch.int32, device="cuda")
+        rtx.camera_rays_device(cam, SEED, region, 0, 1, d_rays.data_ptr(), d_keys.data_ptr(), stream_of(torch))
+        torch.cuda.synchronize()
+        rays = d_rays.cpu().numpy().reshape(-1).view(rtx.RAY_DTYPE).copy()
+        keys = d_keys.cpu().numpy().reshape(-1).view(rtx.KEY_DTYPE).copy()
+        hits, st = dev.trace(rays, rtx.RTX_TRACE_UV, stats=True)
+        assert st.scene_placement == rtx.RTX_SCENE_IN_HBM
+        # the block
+        want = direct_ref.sample(desc, dev.export(), hits, keys, SEED)
+        got, dst = direct_dev(torch, dev, hits, keys, SEED, rtx.RTX_DIRECT_COUNTERS, stats=True)
+        sampled = (want["flags"] & rtx.RTX_DIRECT_SAMPLED) != 0
+        visible = (want["flags"] & rtx.RTX_DIRECT_VISIBLE) != 0
+        print(f"memory scene: {len(want)} records, {int(sampled.sum())} sampled, {int(visible.sum())} visible, "
+              f"{int((sampled & ~visible).sum())} occluded")
+        same_records(got, want)
+        assert (dst.n, dst.sampled, dst.visible, dst.rng_draws) == (P, int(sampled.sum()), int(visible.sum()),
+                                                                    int(want["rng_draws"].sum()))
+        assert visible.sum() > 0 and (sampled & ~visible).sum() > 0  # both outcomes of a shadow walk
+        s = np.nonzero(got["flags"] & rtx.RTX_DIRECT_SAMPLED)[0]
+        any_hit = trace_dev(torch, dev, got["ray"][s].copy(), rtx.RTX_TRACE_ANY)
+        assert np.array_equal((got["flags"][s] & rtx.RTX_DIRECT_VISIBLE) != 0, any_hit["prim"] == rtx.RTX_HIT_NONE)
+        # the fused pass
+        cam.max_depth, cam.samples_per_pixel = 8, 3
+        composed = wavefront.render(dev, cam, 29, region, direct=True).cpu().numpy()
+        acc = dev.accumulator(cam, 29, region)
+        try:
+            acc.add_direct(3)
+            rgb = acc.resolve()[0]
+        finally:
+            acc.close()
+        bad = np.argwhere((rgb.view(np.uint32) != composed.view(np.uint32)).any(axis=2))
+        assert len(bad) == 0, (len(bad), bad[:4].tolist(), [(rgb[y, x], composed[y, x]) for y, x in bad[:3]])
+    finally:
+        dev.close()
+
+
 # ---- the estimator ----------------------------------------------------------------------------------------------
 def test_no_emitters_is_the_plain_render(torch):
     """random_spheres 24 x 13, the caller's tree, depth 8: with no emitter nothing is added and nothing suppressed."""
