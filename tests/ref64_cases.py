@@ -2,7 +2,8 @@
 
 TEST INFRASTRUCTURE.  Small shapes where the code can be wrong, not the workload's: images ragged
 against the 8x8 tile, hand-made camera tables (one kind with defocus, one without), hand-made
-scene tables with a World-list root (spheres first, then quads: the index order ref64 scans).
+scene tables with a World-list root (spheres first, then quads: the index order ref64 scans), and the two
+mixed scenes of tests/big_scenes.py, whose layouts are past the LDS limit (a tree with nested Worlds).
 
 A case is (name, desc pointer, camera, seed, window, spp, cap): `cap` is the share of samples
 that may be left out — 1 % on the probes (one primitive, or one scatterer in an emissive sphere),
@@ -321,6 +322,13 @@ def host_scene(name, width, depth, spp=1):
     return s.desc, s.camera(width=width, spp=spp, depth=depth)
 
 
+def big_scene(case):
+    """The mixed scenes past the LDS limit (tests/big_scenes.py): the kernels that read the scene from HBM."""
+    import big_scenes
+
+    return big_scenes.ref64_scene(case)
+
+
 def _case(name, scene, seed, window=None, spp=1, cap=CAP_PROBE):
     return name, scene, seed, window, spp, cap
 
@@ -360,6 +368,9 @@ CASES = [
     _case("cornell_box_window", lambda: host_scene("cornell_box", 600, 50), 41, window=(300, 340, 24, 12),
           cap=CAP_SCENE),
     _case("earth_window", lambda: host_scene("earth", 400, 50), 43, window=(188, 106, 24, 12), cap=CAP_SCENE),
+    # scenes past the LDS limit (tests/big_scenes.py): a tree with nested Worlds, read from HBM
+    _case("big_mixed", lambda: big_scene("big_mixed"), 5, cap=CAP_SCENE),
+    _case("big_mixed_noise", lambda: big_scene("big_mixed_noise"), 5, cap=CAP_SCENE),
 ]
 NAMES = [c[0] for c in CASES]
 NO_LDS_CASES = ("dielectric_sphere", "random_scene_2")  # the two cases the GPU file also runs from global memory

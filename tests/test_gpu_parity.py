@@ -155,7 +155,9 @@ def test_every_kernel_variant_is_bit_exact(torch_cuda, spheres, dev_spheres, nam
     bits and the same work counters as the oracle."""
     cam = spheres.camera(width=120, spp=6, depth=50)
     reg = rtx.Region(3, 2, 101, 53, 0, 1)
-    check_scene(torch_cuda, dev_spheres, spheres.desc, cam, 17, reg, flags=KERNELS[name])
+    _, st, _ = check_scene(torch_cuda, dev_spheres, spheres.desc, cam, 17, reg, flags=KERNELS[name])
+    want = rtx.RTX_SCENE_IN_HBM if name == "v3-global-scene" else rtx.RTX_SCENE_IN_LDS
+    assert st.scene_placement == want, (st.scene_placement, want)
 
 
 def test_earth_image_texture_and_defocus(torch_cuda, built):
@@ -187,7 +189,8 @@ def test_stress_100k_crop(torch_cuda, built):
     assert dev.device_bytes() > 64 * 1024
     cam = scene.camera(width=1920, spp=2, depth=50)
     reg = rtx.Region(900, 500, 48, 24, 0, 1)
-    check_scene(torch_cuda, dev, scene.desc, cam, 3, reg)
+    _, st, _ = check_scene(torch_cuda, dev, scene.desc, cam, 3, reg)
+    assert st.scene_placement == rtx.RTX_SCENE_LDS_CACHE, st.scene_placement
 
 
 def test_v3_chunked_scratch(torch_cuda, spheres, dev_spheres, monkeypatch):
@@ -244,9 +247,10 @@ def test_stress_100k_lds_cache(torch_cuda, built, monkeypatch, hot):
     assert np.array_equal(gpu, it)
     _, st = gpu_region(torch_cuda, dev, cam, 13, reg, counters=True)
     if hot == "0":
-        assert st.cache_hits == 0
+        assert st.cache_hits == 0 and st.scene_placement == rtx.RTX_SCENE_IN_HBM, st.scene_placement
     else:
         assert 0 < st.cache_hits < st.node_visits + st.prim_tests
+        assert st.scene_placement == rtx.RTX_SCENE_LDS_CACHE, st.scene_placement
 
 
 def project(cam, p):

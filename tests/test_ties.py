@@ -2,7 +2,9 @@
 clipped to the left's hit, strictly) on every walk the library takes of another tree or in another
 storage order: the LDS layouts (entry index = the reference walk's rank), and the HBM layouts, whose
 sphere entries carry a rank word (sphere_test RANK_WORD) — the near tree, the guarded tree and the
-caller's tree read from HBM (RTX_FLAG_NO_LDS) or through the LDS cache of a big scene.
+caller's tree read from HBM (RTX_FLAG_NO_LDS).  This scene fits the LDS copy; the same ties through the
+LDS cache of a big scene, and in its hot-first storage order from HBM alone, are big_scenes.py's big_ties
+(tests/test_big_scenes.py::test_big_ties_matter, tests/test_big_scenes_gpu.py::test_big_ties).
 
 The scene: randSpheres' spheres plus exact copies of its three big spheres with other materials, under
 a NewBVH-shaped tree (median splits, leaves of one or two spheres, boxes the unions of NewSphere's).  A
@@ -25,8 +27,10 @@ def own_box(c, r):
     return np.minimum(p1, p2), np.maximum(p1, p2)
 
 
-def newbvh_desc(spheres, materials, base_desc):
-    """A scene description whose tree is NewBVH-shaped over `spheres` (list of (centre, r, material))."""
+def newbvh_desc(spheres, materials, base_desc, leaf=2, order=None):
+    """A scene description whose tree is NewBVH-shaped over `spheres` (list of (centre, r, material)); leaf=1: every
+    leaf a one-element split; order: the spheres' order before the first (stable) sort, which spheres with equal
+    boxes keep — by default their index order, so that of two exact copies the walk meets the lower index first."""
     n = len(spheres)
     sph = (rtx.Sphere * n)()
     for i, (c, r, m) in enumerate(spheres):
@@ -41,7 +45,7 @@ def newbvh_desc(spheres, materials, base_desc):
         ids = sorted(ids, key=lambda i: -float(boxes[i][0][ax]))  # descending box minimum, stable
         me = len(nodes)
         nodes.append(None)
-        if len(ids) <= 2:
+        if len(ids) <= leaf:
             kids = [rtx.ref_prim(rtx.RTX_PRIM_SPHERE, i) for i in ids]
             if len(kids) == 1:
                 kids.append(kids[0])  # a one-element split: left == right (bvh.go:162-165)
@@ -56,7 +60,7 @@ def newbvh_desc(spheres, materials, base_desc):
         nodes[me] = (lo.astype(F), hi.astype(F), kids)
         return me
 
-    root = build(list(range(n)), 0)
+    root = build(list(range(n)) if order is None else list(order), 0)
     arr = (rtx.BvhNode * len(nodes))()
     for i, (lo, hi, kids) in enumerate(nodes):
         arr[i].bmin = (ctypes.c_float * 3)(*[float(v) for v in lo])
