@@ -61,7 +61,10 @@ enum {
 
 /* A BVH interior node exactly as internal/bvh.go:132-185 builds it: an AABB
  * (bvh.go:36-50, from NewAabbFromBoxes) and two children.  A one-element split
- * produces left == right (bvh.go:162-165); that is kept as-is in the table.   32 B */
+ * produces left == right (bvh.go:162-165); that is kept as-is in the table.
+ * Every reachable node's box is ordered, bmin[k] <= bmax[k] on each axis, as NewAabb
+ * makes it (flat and infinite boxes included); a node with bmin[k] > bmax[k] or a NaN
+ * bound is rejected with RTX_ERR_INVALID_ARG.                                 32 B */
 typedef struct rtx_bvh_node {
     float bmin[3];
     int32_t left;

@@ -35,7 +35,7 @@ __device__ __forceinline__ V3 cross(V3 l, V3 r) {                               
 }
 // 1 / x, correctly rounded.  When every active lane's |x| lies in [2^-125, 2^125] (exponent
 // field 2..252): one Newton step with fma on v_rcp_f32 (3 VALU), which equals the IEEE quotient
-// on all 4.2e9 such inputs (scripts/micro/fastrcp_check.hip, exhaustive on the GPU); else the
+// on all 4.2e9 such inputs (tests/test_device_math_gpu.py, exhaustive on the GPU); else the
 // compiler's division (~10 VALU).  The vote is wave-uniform, so the branch does not diverge.
 // (rcp_exp_off: the exponent field less 2, so that the largest of several values' offsets decides for all of them)
 __device__ __forceinline__ uint32_t rcp_exp_off(float x) { return ((__float_as_uint(x) >> 23) & 0xFFu) - 2u; }
@@ -50,9 +50,11 @@ __device__ __forceinline__ float rcp_ieee(float x) {
 }
 // sqrt(x) correctly rounded, as the compiler expands an f32 sqrt: v_sqrt, then the neighbour
 // whose fma residual changes sign.  The expansion's 2^32 pre-scaling is needed only below 2^-96,
-// so it runs (the builtin) only when a lane of the wave has 0 <= x < 2^-96; its +-0 / +inf
+// so it runs (the builtin) only when a lane of the wave has |x| < 2^-96; its +-0 / +inf
 // pass-through is left out: v_sqrt returns those exactly and both residuals then keep them.
-__device__ __forceinline__ float sqrt_rn_fast(float x) {  // x >= 2^-96 (a negative or NaN x: NaN)
+// (|x|, not 0 <= x: v_sqrt_f32 turns a negative subnormal into -0 where IEEE says NaN — found by
+// tests/test_device_math_gpu.py, exhaustive on the GPU, which holds both forms to the builtin.)
+__device__ __forceinline__ float sqrt_rn_fast(float x) {  // |x| >= 2^-96 (x <= -2^-96 or NaN: NaN), or -0
     float s = __builtin_amdgcn_sqrtf(x);
     const float sp = __uint_as_float(__float_as_uint(s) - 1u), sn = __uint_as_float(__float_as_uint(s) + 1u);
     const float rp = __builtin_fmaf(-sp, s, x), rn = __builtin_fmaf(-sn, s, x);
@@ -61,7 +63,7 @@ __device__ __forceinline__ float sqrt_rn_fast(float x) {  // x >= 2^-96 (a negat
     return s;
 }
 __device__ __forceinline__ float sqrt_rn(float x) {
-    if (__builtin_amdgcn_ballot_w64(x < 0x1p-96f && x >= 0.0f) != 0) return __builtin_sqrtf(x);
+    if (__builtin_amdgcn_ballot_w64(__builtin_fabsf(x) < 0x1p-96f) != 0) return __builtin_sqrtf(x);
     return sqrt_rn_fast(x);
 }
 // Unit (vec3.go:103-113): v * (1 / sqrt(lensq(v))), both correctly rounded.  One vote on q = lensq(v) decides both
@@ -70,10 +72,12 @@ __device__ __forceinline__ float sqrt_rn(float x) {
 // rcp_ieee's vote is implied.  Else the compiler's sqrt and division for the whole wave: the fast forms equal them
 // wherever they apply, so a lane's bits do not depend on the side its wave took.  (Two votes, sqrt_rn's and
 // rcp_ieee's, each with its compares and branch, cost the headline step 0.55 ms: DESIGN.md §38.)
+__device__ __forceinline__ bool unit_fast_ok(float q) {  // 2^-96 <= q < inf
+    return __float_as_uint(q) - 0x0F800000u < 0x7F800000u - 0x0F800000u;
+}
 __device__ __forceinline__ V3 unit(V3 v) {
     const float q = lensq(v);
-    const bool fast = __float_as_uint(q) - 0x0F800000u < 0x7F800000u - 0x0F800000u;
-    if (__builtin_amdgcn_ballot_w64(!fast) == 0) return scale(v, rcp_newton(sqrt_rn_fast(q)));
+    if (__builtin_amdgcn_ballot_w64(!unit_fast_ok(q)) == 0) return scale(v, rcp_newton(sqrt_rn_fast(q)));
     return scale(v, 1.0f / __builtin_sqrtf(q));
 }
 __device__ __forceinline__ bool near_zero(V3 v) {                                                  // vec3.go:170-172
@@ -991,10 +995,15 @@ __device__ __forceinline__ void quad_test(Trav& t, const Ray& r, const SceneRef 
 
 // n / a correctly rounded, given y = RN(1 / a) (Markstein: q0 = RN(n y) is within 1 ulp of n / a,
 // the residual e = n - a q0 is exact by fma, and RN(q0 + e y) = RN(n / a) when y is the
-// correctly rounded reciprocal), for a in [2^-60, 2^60] (Trav::safe): every quotient that can
-// pass `tmin < t < closest` is then a normal number and so exactly the division's.  Quotients
-// that overflow may come out NaN instead of inf, which fails the same tests.  3 VALU instead
-// of the 11 of a division (scripts/micro/fastdiv_check.hip checks it against v_div_* on the GPU).
+// correctly rounded reciprocal), for a in [2^-60, 2^60] (Trav::safe) and 2^-102 <= |n| <= 2^65: a
+// normal quotient is then exactly the division's, and a zero, subnormal or overflowing one stays
+// non-normal (an overflow may come out NaN instead of inf, which fails the same tests).  Below
+// |n| = 2^-102 the residual, a multiple of ulp(a) ulp(q0), may fall under 2^-149 and round; a
+// quotient within two ulps of 2^128 may overflow in n y.  The sphere test stays inside: a finite
+// disc has |hb|, sqrt(disc) < 2^64, so |n| < 2^65 (an infinite one gives inf or NaN both ways), and
+// a root past tmin has |n| > tmin a >= 2^-102 for tmin >= 2^-42 (a render's 0.001; rtx_trace.hip
+// keeps a ray with a smaller tmin off the fast forms).  3 VALU instead of the 11 of a division
+// (tests/test_device_math_gpu.py checks it against v_div_* on the GPU).
 __device__ __forceinline__ float div_by(float n, float a, float y) {
     const float q0 = n * y;
     const float e = __builtin_fmaf(-a, q0, n);
@@ -1004,7 +1013,7 @@ __device__ __forceinline__ float div_by(float n, float a, float y) {
 // (*Sphere).Hit, hittables.go:96-116, of the sphere entry (ea, eb) at `pos` against (tmin, closest).
 // tmin (here, in quad_test and in box_hit): a render's 0.001 (ray.go:37) by default, a constant that folds
 // into every render kernel as before; the ray queries (rtx_trace.hip) pass each ray's own.
-// SAFE: the two divisions by a as div_by (needs tmin >= 2^-126: an accepted quotient is then normal).
+// SAFE: the two divisions by a as div_by (needs tmin >= 2^-42: an accepted root is then inside div_by's claim).
 // RANKED (the LDS layout, whose primitives are stored in the reference walk's order): a root equal
 // to `closest` also wins when the sphere comes before the current hit in the reference's order —
 // the tie bvh.go:220-249 resolves for the sphere it meets first (the right subtree is clipped to the
@@ -1288,11 +1297,13 @@ __device__ __forceinline__ uint32_t trav_step_batched(Trav& t, const Ray& r, con
 //   - sphere (sphere_test<false, true>): hb, c, disc as hittables.go:97-102; sqrt correctly
 //     rounded as the compiler expands an f32 sqrt — v_sqrt, then the neighbour whose fma
 //     residual changes sign; inputs below 2^-96 scaled by 2^32 first and the root by 2^-16
-//     after, a path taken only when some lane has 0 <= disc < 2^-96.  (The expansion's last
+//     after, a path taken only when some lane has |disc| < 2^-96.  (The expansion's last
 //     step, passing +-0 and +inf through, is left out: v_sqrt returns them exactly and both
 //     neighbour residuals are then NaN or a zero, which keeps them.)  Both roots by div_by;
 //     the first root when tmin < t1, else the second (hittables.go:110-114).  disc < 0 needs no
-//     test of its own (:104): v_sqrt returns NaN there, and NaN roots fail tmin < t.
+//     test of its own (:104): v_sqrt returns NaN there, and NaN roots fail tmin < t — but only
+//     for a normal disc: v_sqrt_f32 flushes a negative subnormal to -0 and returns -0, a root the
+//     reference never takes.  Hence |disc|: scaled by 2^32 it is normal again, and its root NaN.
 // gfx950 hazards: a VALU-written SGPR/VCC read as a v_cndmask mask by the next VALU needs
 // s_nop 1; a v_sqrt result read by the next VALU needs s_nop 0 (as the compiler emits them).
 // Entry read of the prefetching walk, under the current exec: both halves from the fixed layout.
@@ -1408,8 +1419,8 @@ __device__ __forceinline__ uint32_t trav_step_batched(Trav& t, const Ray& r, con
         "v_mul_f32 v9, v8, v8\n\t"                                           \
         "v_sub_f32 v10, v9, v10\n\t"                                         \
         "v_sqrt_f32_e32 v12, v10\n\t"                                        \
-        "v_cmp_gt_u32_e32 vcc, 0xf800000, v10\n\t" /* 0 <= x < 2^-96 (by its bits; in the v_sqrt hazard slot) */\
-        "s_cbranch_vccnz LS%=_" #K "\n\t" /* here: x >= 2^-96, -0 or x < 0 (NaN root: no hit) */\
+        "v_cmp_gt_f32_e64 vcc, %[tiny], |v10|\n\t" /* |x| < 2^-96 (in the v_sqrt hazard slot) */\
+        "s_cbranch_vccnz LS%=_" #K "\n\t" /* here: x >= 2^-96, or x <= -2^-96 or NaN (NaN root: no hit) */\
         "v_add_u32_e32 v9, -1, v12\n\t"                                      \
         "v_add_u32_e32 v11, 1, v12\n\t"                                      \
         "v_fma_f32 v13, -v9, v12, v10\n\t"                                   \
@@ -1495,8 +1506,8 @@ __device__ __forceinline__ uint32_t trav_step_batched(Trav& t, const Ray& r, con
         "v_mul_f32 v9, v8, v8\n\t"                                           \
         "v_sub_f32 v10, v9, v10\n\t"                                         \
         "v_sqrt_f32_e32 v12, v10\n\t"                                        \
-        "v_cmp_gt_u32_e32 vcc, 0xf800000, v10\n\t" /* 0 <= x < 2^-96 (by its bits; in the v_sqrt hazard slot) */\
-        "s_cbranch_vccnz LS%=_" #K "\n\t" /* here: x >= 2^-96, -0 or x < 0 (NaN root: no hit) */\
+        "v_cmp_gt_f32_e64 vcc, %[tiny], |v10|\n\t" /* |x| < 2^-96 (in the v_sqrt hazard slot) */\
+        "s_cbranch_vccnz LS%=_" #K "\n\t" /* here: x >= 2^-96, or x <= -2^-96 or NaN (NaN root: no hit) */\
         "v_add_u32_e32 v9, -1, v12\n\t"                                      \
         "v_add_u32_e32 v11, 1, v12\n\t"                                      \
         "v_fma_f32 v13, -v9, v12, v10\n\t"                                   \
@@ -1637,7 +1648,8 @@ __device__ __forceinline__ uint32_t trav_step_batched(Trav& t, const Ray& r, con
 #define RTX_WALK_INS                                                                                         \
     [ox] "v"(r.o.x), [oy] "v"(r.o.y), [oz] "v"(r.o.z), [dx] "v"(r.d.x), [dy] "v"(r.d.y), [dz] "v"(r.d.z),  \
         [ix] "v"(t.ix), [iy] "v"(t.iy), [iz] "v"(t.iz), [a] "v"(t.a), [ra] "v"(t.ra), [end] "s"(end),      \
-        [kmin] "s"(kmin), [tmin] "s"(tmin), [W] "s"(W), [P0] "s"(P0), [thresh] "s"(thresh), [pe] "s"(prim_end)
+        [kmin] "s"(kmin), [tmin] "s"(tmin), [W] "s"(W), [P0] "s"(P0), [thresh] "s"(thresh), [pe] "s"(prim_end),  \
+        [tiny] "s"(0x1p-96f)
 #define RTX_WALK_CLOBBERS                                                                                    \
     "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15",    \
         "v16", "vcc", "scc"
@@ -1661,10 +1673,10 @@ __device__ __forceinline__ uint32_t trav_step_batched(Trav& t, const Ray& r, con
         S(5, RTX_BOX_FAST(5, 6)) S(6, RTX_BOX_FAST(6, 7)) S(7, RTX_BOX_NEXT(7))
 #define RTX_WALK_BLOCK_(n) RTX_WALK_##n
 #define RTX_WALK_BLOCK(n) RTX_WALK_BLOCK_(n)
-// The sqrt of a primitive step when some lane has 0 <= disc < 2^-96 (scaled by 2^32), out of the
+// The sqrt of a primitive step when some lane has |disc| < 2^-96 (scaled by 2^32), out of the
 // hot path: placed after the loop, it returns to the step (one taken branch fewer per step).
 #define RTX_WALK_COLD(K)                                                     \
-        "LS%=_" #K ":\n\t" /* some lane: 0 <= x < 2^-96, scaled by 2^32 */   \
+        "LS%=_" #K ":\n\t" /* some lane: |x| < 2^-96, scaled by 2^32 */      \
         "v_mul_f32 v13, 0x4f800000, v10\n\t"                                 \
         "v_cndmask_b32_e32 v13, v10, v13, vcc\n\t"                           \
         "v_sqrt_f32_e32 v12, v13\n\t"                                        \

@@ -164,7 +164,7 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void direct_lights(DirectParams p)
         const float tmin = 0.001f;
         Trav t;
         trav_begin(t, r, sampled ? p.scene.start : end);
-        t.safe = t.safe && tmin >= 0x1p-126f;  // as trace_rays: the fast step forms need every accepted root normal
+        t.safe = t.safe && tmin >= 0x1p-42f;  // as trace_rays: the fast step forms need every accepted root in div_by's claim
         t.closest = 0.999f;                    // the running bound starts at the ray's tmax
         Counters cnt{0, 0, 0, 0, 0, 0, 0};
         while (ballot(t.i < end) != 0)

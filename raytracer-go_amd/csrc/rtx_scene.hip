@@ -137,6 +137,12 @@ int emit(const rtx_scene_desc* d, int32_t root, std::vector<rtx_entry>& out) {
             for (uint32_t k = l.count; k-- > 0;) stack.push_back({d->list_refs[l.first + k], -1});
         } else if (f.ref >= 0) {
             const rtx_bvh_node& n = d->nodes[f.ref];
+            // NewAabb orders every axis (bvh.go:36-50); the walk's med3 slab form (box_hit) relies on it: a box with
+            // bmin > bmax misses in the reference and would hit there.  (`!(<=)` rejects a NaN bound too.)
+            for (int k = 0; k < 3; ++k)
+                if (!(n.bmin[k] <= n.bmax[k]))
+                    return fail(RTX_ERR_INVALID_ARG, "node %d: box axis %d is not ordered (bmin %g, bmax %g)", f.ref, k,
+                                (double)n.bmin[k], (double)n.bmax[k]);
             e.a[0] = n.bmin[0]; e.a[1] = n.bmin[1]; e.a[2] = n.bmin[2];
             e.b[0] = n.bmax[0]; e.b[1] = n.bmax[1]; e.b[2] = n.bmax[2];
             const int32_t tag = RTX_E_NODE;

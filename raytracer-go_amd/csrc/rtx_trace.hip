@@ -110,8 +110,9 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void trace_rays(TraceParams p) {
             }
             Trav nt;
             trav_begin(nt, nq.r, p.scene.start);  // (whole wave: its votes)
-            // the fast step forms (med3 boxes, div_by roots) also need every accepted root normal: tmin >= 2^-126
-            nt.safe = nt.safe && nq.tmin >= 0x1p-126f;
+            // the fast step forms (med3 boxes, div_by roots) also need every accepted root inside div_by's claim:
+            // |n| = |root| a >= 2^-102 (rtx_device.h), so tmin >= 2^-42 for a >= 2^-60
+            nt.safe = nt.safe && nq.tmin >= 0x1p-42f;
             nt.closest = tmax;  // the running bound starts at the ray's tmax
             if (take) {
                 q = nq;

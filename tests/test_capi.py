@@ -160,6 +160,32 @@ def test_bad_refs_and_cycles(built):
     assert rc == rtx.RTX_ERR_INVALID_ARG
 
 
+def test_node_boxes_must_be_ordered(built):
+    """A node's box is ordered on every axis, as NewAabb makes it (rtx.h): the walk's med3 slab form hits a box with
+    bmin > bmax that the reference misses.  Ordered, infinite and flat boxes are accepted."""
+    inf, nan = float("inf"), float("nan")
+
+    def one_node(bmin, bmax):
+        n = rtx.BvhNode()
+        n.bmin[:], n.bmax[:] = bmin, bmax
+        n.left, n.right = rtx.ref_prim(0, 0), rtx.ref_prim(0, 1)
+        unused = rtx.BvhNode()  # not reachable from the root: never checked
+        unused.bmin[:], unused.bmax[:] = [1, 1, 1], [0, 0, 0]
+        unused.left = unused.right = rtx.ref_prim(0, 0)
+        return create(make_desc([sphere(), sphere()], [lambertian()], [texture()], nodes=[n, unused], roots=[0]))
+
+    for bmin, bmax in (([-1, -1, -2], [1, 1, 0]), ([-inf, -inf, -inf], [inf, inf, inf]), ([-1, 0.5, -2], [1, 0.5, 0]),
+                       ([-0.0, -1, -2], [0.0, 1, 0]), ([0.0, -1, -2], [-0.0, 1, 0]), ([inf, -1, -2], [inf, 1, 0])):
+        rc, msg = one_node(bmin, bmax)
+        assert rc != rtx.RTX_ERR_INVALID_ARG and "not ordered" not in msg, (bmin, bmax, msg)
+    for axis in range(3):
+        for lo, hi in ((1.0, 0.5), (inf, -inf), (1e-45, 0.0), (nan, 1.0), (-1.0, nan), (nan, nan)):
+            bmin, bmax = [-1.0, -1.0, -2.0], [1.0, 1.0, 0.0]
+            bmin[axis], bmax[axis] = lo, hi
+            rc, msg = one_node(bmin, bmax)
+            assert rc == rtx.RTX_ERR_INVALID_ARG and f"node 0: box axis {axis} is not ordered" in msg, (bmin, bmax, msg)
+
+
 def test_empty_scene(built):
     rc, _ = create(make_desc([sphere()], [lambertian()], [texture()], roots=[]))
     assert rc == rtx.RTX_ERR_INVALID_ARG

@@ -14,32 +14,10 @@ import pytest
 
 import oracle_binding as ob
 import rtx
+from device_math_ref import aabb_hit
 
 F = np.float32
 PATH = ("samples", "segments", "hits", "texel_fetches", "rng_draws", "prim_tests")
-
-
-def in_boundary(d, o, lo, hi, tmin, tmax):
-    """InBoundary (bvh.go:84-102) in float32, elementwise."""
-    with np.errstate(all="ignore"):
-        inv = F(1) / d
-        t0, t1 = (lo - o) * inv, (hi - o) * inv
-        sw = inv < 0
-        t0, t1 = np.where(sw, t1, t0), np.where(sw, t0, t1)
-        tmin = np.where(t0 > tmin, t0, tmin)
-        tmax = np.where(t1 < tmax, t1, tmax)
-    return tmin < tmax, tmin, tmax
-
-
-def aabb_hit(o, d, lo, hi, tmin, tmax):
-    ok = np.ones(len(o), bool)
-    tmin = np.full(len(o), tmin, F)
-    tmax = np.full(len(o), tmax, F)
-    for k in range(3):
-        hit, a, b = in_boundary(d[:, k], o[:, k], lo[:, k], hi[:, k], tmin, tmax)
-        tmin, tmax = np.where(ok, a, tmin), np.where(ok, b, tmax)
-        ok &= hit
-    return ok
 
 
 def test_slab_test_is_monotone_in_the_box():

@@ -22,6 +22,7 @@ import pytest
 
 import oracle_binding as ob
 import rtx
+from hand_scenes import Materials, plain_camera, sphere_desc
 from parity import check_scene, gpu_region
 
 pytestmark = pytest.mark.gpu
@@ -91,71 +92,6 @@ def test_cornell_box(torch_cuda, built):
 
 
 # ---- the glass scene ------------------------------------------------------------------------------------------------
-def f3(a):
-    return [float(F(x)) for x in a]
-
-
-class Materials(list):
-    def add(self, kind, albedo=(1.0, 1.0, 1.0), fuzz=0.0, ior=1.0):
-        m = rtx.Material()
-        m.type, m.texture, m.fuzz, m.ior = kind, 0, float(F(fuzz)), float(F(ior))
-        m.albedo[:] = f3(albedo)
-        self.append(m)
-        return len(self) - 1
-
-
-def sphere_desc(balls, mats):
-    """A scene description of the spheres (centre, radius, material index) under a median-split tree."""
-    tex = rtx.Texture()
-    tex.type = rtx.RTX_TEX_SOLID
-    tex.even[:] = [0.5, 0.5, 0.5]
-    spheres, prims = [], []
-    for i, (c, r, mat) in enumerate(balls):
-        s = rtx.Sphere()
-        c, r = np.array(c, F), F(r)
-        s.center[:] = f3(c)
-        s.radius = float(r)
-        s.material = mat
-        spheres.append(s)
-        prims.append((rtx.ref_prim(rtx.RTX_PRIM_SPHERE, i), c - r, c + r))
-    nodes = []
-
-    def build(items, depth):
-        if len(items) == 1:
-            return items[0]
-        items = sorted(items, key=lambda it: float(it[1][(0, 2, 1)[depth % 3]]))
-        mid = len(items) // 2
-        me = len(nodes)
-        nodes.append(None)
-        lref, lmin, lmax = build(items[:mid], depth + 1)
-        rref, rmin, rmax = build(items[mid:], depth + 1)
-        bmin, bmax = np.minimum(lmin, rmin), np.maximum(lmax, rmax)
-        nd = rtx.BvhNode()
-        nd.bmin[:] = f3(bmin)
-        nd.bmax[:] = f3(bmax)
-        nd.left, nd.right = lref, rref
-        nodes[me] = nd
-        return me, bmin, bmax
-
-    root, _, _ = build(prims, 0)
-    d = rtx.SceneDesc()
-    keep = []
-
-    def arr(ctype, items):
-        a = (ctype * max(1, len(items)))(*items)
-        keep.append(a)
-        return a
-
-    d.nodes, d.n_nodes = arr(rtx.BvhNode, nodes), len(nodes)
-    d.roots, d.n_roots = arr(ctypes.c_int32, [root]), 1
-    d.spheres, d.n_spheres = arr(rtx.Sphere, spheres), len(spheres)
-    d.quads, d.n_quads = arr(rtx.Quad, []), 0
-    d.materials, d.n_materials = arr(rtx.Material, mats), len(mats)
-    d.textures, d.n_textures = arr(rtx.Texture, [tex]), 1
-    d._keep = keep
-    return d
-
-
 def glass_scene():
     """A Lambertian ground, a 5 x 3 field of glass spheres (ior 1.5, every fourth 2.4), three larger glass spheres with
     a Lambertian core off their centre, one Metal sphere."""
@@ -215,17 +151,6 @@ def test_glass_scene(torch_cuda, built):
 
 
 # ---- the general side of the two merged votes -----------------------------------------------------------------------
-def plain_camera(w, h, spp, depth, origin, p00, du, dv):
-    cam = rtx.Camera()
-    cam.image_width, cam.image_height, cam.samples_per_pixel, cam.max_depth = w, h, spp, depth
-    cam.center[:] = f3(origin)
-    cam.pixel00[:] = f3(p00)
-    cam.pixel_du[:] = f3(du)
-    cam.pixel_dv[:] = f3(dv)
-    cam.background[:] = [0.6, 0.7, 0.9]
-    return cam
-
-
 def test_trav_begin_division_side(torch_cuda, built):
     """Every camera ray lies in the plane z = 0 (the pixel grid's plane holds the camera): direction.z is exactly 0,
     outside rcp_newton's domain, so every wave that begins camera segments takes trav_begin's vote to the division
