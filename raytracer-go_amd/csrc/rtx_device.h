@@ -342,6 +342,47 @@ __device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c
     }
     return U4{c0, c1, c2, c3};
 }
+// Two blocks under one key whose counters differ only in c3: (c0, c1, c2, c3) and (c0, c1, c2, c3b), bit for bit
+// what two calls give.  One chain of 10 dependent multiply / xor pairs leaves the VALU nothing to issue into the
+// multiplies' latency; here the two chains alternate, and the scalar side (the opaque key, the 18 key bumps) runs
+// once.  The first round's two products are the same in both chains and c3 enters it only through n2's xor; the
+// second round's product with c0 is shared too.
+struct U4x2 {
+    U4 a, b;
+};
+__device__ __forceinline__ U4x2 philox4x32_10_x2(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t c3b,
+                                                 uint32_t k0, uint32_t k1) {
+    if (RTX_PHILOX_OPAQUE) asm volatile("" : "+s"(k0), "+s"(k1));
+    const uint64_t q0 = (uint64_t)0xD2511F53u * c0;
+    const uint64_t q1 = (uint64_t)0xCD9E8D57u * c2;
+    uint32_t a0 = __builtin_amdgcn_bitop3_b32((uint32_t)(q1 >> 32), c1, k0, 0x96), b0 = a0;
+    uint32_t a1 = (uint32_t)q1, b1 = a1;
+    uint32_t a2 = __builtin_amdgcn_bitop3_b32((uint32_t)(q0 >> 32), c3, k1, 0x96);
+    uint32_t b2 = __builtin_amdgcn_bitop3_b32((uint32_t)(q0 >> 32), c3b, k1, 0x96);
+    uint32_t a3 = (uint32_t)q0, b3 = a3;
+#pragma unroll
+    for (int r = 1; r < 10; ++r) {
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+        const uint64_t pa0 = (uint64_t)0xD2511F53u * a0;
+        const uint64_t pb0 = (uint64_t)0xD2511F53u * b0;
+        const uint64_t pa1 = (uint64_t)0xCD9E8D57u * a2;
+        const uint64_t pb1 = (uint64_t)0xCD9E8D57u * b2;
+        const uint32_t na0 = __builtin_amdgcn_bitop3_b32((uint32_t)(pa1 >> 32), a1, k0, 0x96);
+        const uint32_t nb0 = __builtin_amdgcn_bitop3_b32((uint32_t)(pb1 >> 32), b1, k0, 0x96);
+        const uint32_t na2 = __builtin_amdgcn_bitop3_b32((uint32_t)(pa0 >> 32), a3, k1, 0x96);
+        const uint32_t nb2 = __builtin_amdgcn_bitop3_b32((uint32_t)(pb0 >> 32), b3, k1, 0x96);
+        a0 = na0;
+        a1 = (uint32_t)pa1;
+        a2 = na2;
+        a3 = (uint32_t)pa0;
+        b0 = nb0;
+        b1 = (uint32_t)pb1;
+        b2 = nb2;
+        b3 = (uint32_t)pb0;
+    }
+    return U4x2{U4{a0, a1, a2, a3}, U4{b0, b1, b2, b3}};
+}
 __device__ __forceinline__ float unit_f32(uint32_t w) { return (float)(w >> 8) * 0x1.0p-24f; }
 // RandF32N(-1, 1), math.go:30-32: -1 + u * (1 - (-1)).  u * 2 is exact (u = n * 2^-24, n < 2^24), so the two
 // multiplies are one by 2^-23: the same bits, one VALU fewer per word.
@@ -351,6 +392,9 @@ struct PathRng {
     uint32_t k0, k1, pixel, sample;
     __device__ __forceinline__ U4 block(uint32_t event, uint32_t attempt) const {
         return philox4x32_10(pixel, sample, event, attempt, k0, k1);
+    }
+    __device__ __forceinline__ U4x2 block2(uint32_t event, uint32_t attempt, uint32_t attempt_b) const {
+        return philox4x32_10_x2(pixel, sample, event, attempt, attempt_b, k0, k1);
     }
 };
 
@@ -774,24 +818,32 @@ __device__ __forceinline__ CoopPick coop_pick(const CoopRound& r, uint64_t good,
 }
 
 // Wave-cooperative rejection sampling for NewVec3UnitRandOnUnitSphere32 (vec3.go:182-190).
-// Must be called by the whole wave (converged).  A lane with hit >= 0 draws block (e, 0);
-// its words 0-2 are attempt 0 of the unit-sphere loop.  The loop's result is the FIRST
-// accepted attempt a, attempt a being words 0-2 of block (e, a) — a pure function of the
-// counter, so any lane can evaluate any lane's attempt.  Instead of every lane looping
-// until the unluckiest one accepts (acceptance pi/6 per attempt: ~6-7 rounds for 40
-// lanes), the n lanes still rejecting get 64/n consecutive lanes each, which evaluate
-// attempts base .. base+64/n-1 of that owner in one round; the owner takes the first
-// accepted one.  Same attempt, same bits, about 3 Philox rounds per phase.
+// Must be called by the whole wave (converged).  The loop's result is the FIRST accepted
+// attempt a, attempt a being words 0-2 of block (e, a) — a pure function of the counter,
+// so any lane can evaluate any lane's attempt.  A lane with hit >= 0 draws blocks (e, 0)
+// and (e, 1) in one interleaved pass (philox4x32_10_x2) and takes the first of its own
+// attempts 0 and 1 that is accepted: acceptance is pi/6, so of ~36 owners ~8 are left
+// instead of ~17, and the second chain is VALU work issued into the first chain's latency,
+// with no scalar work, cross-lane traffic or wait added.  Instead of every
+// lane looping until the unluckiest one accepts, the n lanes still rejecting then get 64/n
+// consecutive lanes each, which evaluate attempts base .. base+64/n-1 of that owner in one
+// round, from base = 2; the owner takes the first accepted one.  Same attempt, same bits,
+// about one cooperative round per phase.
 template <bool QUADS>
 __device__ __forceinline__ Scatter coop_scatter(const Params& p, const SceneRef E, const PathRng& rng,
                                                 uint32_t e, int32_t hit) {
     Scatter out{v3(0.0f, 0.0f, 0.0f), 0u, 0u};
     float x = 0.0f, y = 0.0f, z = 0.0f;
+    float x1 = 0.0f, y1 = 0.0f, z1 = 0.0f;
     uint32_t ty = 0xFFFFFFFFu;  // (no hit: no material)
     if (hit >= 0) {
         const uint32_t mi = hit_material<QUADS>(E, (uint32_t)hit);
         ty = E.m[mi].type;
-        const U4 b0 = rng.block(e, 0u);
+        const U4x2 b01 = rng.block2(e, 0u, 1u);
+        const U4 b0 = b01.a;
+        x1 = signed_unit(b01.b.x);
+        y1 = signed_unit(b01.b.y);
+        z1 = signed_unit(b01.b.z);
         out.u0 = b0.x;
         x = signed_unit(b0.x);
         y = signed_unit(b0.y);
@@ -801,10 +853,18 @@ __device__ __forceinline__ Scatter coop_scatter(const Params& p, const SceneRef 
     const bool need = ty < 2u;  // Lambertian or Metal (a single compare: its ballot needs no lane-mask materialisation)
     uint32_t att = 0;
     const bool ok0 = x * x + y * y + z * z < 1.0f;  // lensq(v) < 1
-    bool pending = need && !ok0;
-    uint64_t pend = ballot(need) & ~ballot(ok0);  // = ballot(pending)
+    const bool ok1 = x1 * x1 + y1 * y1 + z1 * z1 < 1.0f;
+    if (!ok0) {  // attempt 1, or still rejecting: the loop below then replaces both
+        x = x1;
+        y = y1;
+        z = z1;
+        att = 1u;
+    }
+    bool pending = need && !ok0 && !ok1;
+    // = ballot(pending), from ballots of single compares combined on SALU
+    uint64_t pend = ballot(need) & ~ballot(ok0) & ~ballot(ok1);
     const uint32_t lane = __lane_id();
-    for (uint32_t base = 1; pend != 0;) {
+    for (uint32_t base = 2; pend != 0;) {
         const CoopRound cr = coop_round(pend, pending, lane);
         const uint32_t opix = lane_pull(cr.owner, rng.pixel), osmp = lane_pull(cr.owner, rng.sample);
         const uint32_t oe = lane_pull(cr.owner, e);
