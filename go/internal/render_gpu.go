@@ -774,6 +774,81 @@ func DirectBatch(world Hittable, hits []HitInfo, keys []PathKey, seed uint64) ([
 	return out, nil
 }
 
+// EmitterWeight is the power-heuristic weight of a bounce that found an emitter (rtx_emitter_weight_record, rtx.h
+// "multiple importance sampling of the direct light"): the emission the bounce adds is Emitted * Weight, and the light
+// sample at the hit the bounce left is weighted 1 / (1 + Geom*Geom) of its own DirectSample.Geom.  Weighted false:
+// Weight is 1 (nothing to share the emitter point with) and Geom 0.  Light is the emitter table's index of the
+// primitive found, or NoLight.
+type EmitterWeight struct {
+	Weighted     bool
+	Weight, Geom float32
+	Light        uint32
+}
+
+// NoLight is EmitterWeight.Light of a primitive the emitter table does not hold (RTX_LIGHT_NONE).
+const NoLight = uint32(C.RTX_LIGHT_NONE)
+
+// EmitterWeights traces bounces[i] (with GetColor's Interval{0.001, +Inf}) on the GPU and weights what it found
+// against a light sample at from[i], the Lambertian hit the bounce left (rtx_trace, then rtx_emitter_weight).  HitInfo
+// does not name its primitive, which the weight's area lookup needs: hence the trace here, not a slice of hits.  The
+// world is flattened and uploaded for the call, as in HitBatch.
+func EmitterWeights(world Hittable, from []HitInfo, bounces []Ray) ([]EmitterWeight, error) {
+	if len(from) != len(bounces) {
+		return nil, errors.New("rtx: EmitterWeights needs one bounce ray per hit")
+	}
+	out := make([]EmitterWeight, len(from))
+	if len(from) == 0 {
+		return out, nil
+	}
+	scene, t, err := sceneTables(world, 0)
+	if errors.Is(err, errUnsupported) {
+		return nil, errFallback
+	}
+	if err != nil {
+		return nil, err
+	}
+	defer C.rtx_scene_destroy(scene)
+	n := uintptr(len(from))
+	rayBuf, rayPtr := alignedBytes(n * unsafe.Sizeof(C.rtx_ray{}))
+	fromBuf, fromPtr := alignedBytes(n * unsafe.Sizeof(C.rtx_hit{}))
+	hitBuf, hitPtr := alignedBytes(n * unsafe.Sizeof(C.rtx_hit{}))
+	outBuf, outPtr := alignedBytes(n * unsafe.Sizeof(C.rtx_emitter_weight_record{}))
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pin.Pin(&rayBuf[0])
+	pin.Pin(&fromBuf[0])
+	pin.Pin(&hitBuf[0])
+	pin.Pin(&outBuf[0])
+	inRays, inFrom, found := (*C.rtx_ray)(rayPtr), (*C.rtx_hit)(fromPtr), (*C.rtx_hit)(hitPtr)
+	weights := (*C.rtx_emitter_weight_record)(outPtr)
+	crays, cfrom := unsafe.Slice(inRays, len(from)), unsafe.Slice(inFrom, len(from))
+	for i := range from {
+		crays[i] = C.rtx_ray{origin: vec(bounces[i].origin), tmin: 0.001, dir: vec(bounces[i].dir), tmax: C.float(math.Inf(1))}
+		cfrom[i] = C.rtx_hit{t: C.float(math.Inf(1)), prim: C.RTX_HIT_NONE}
+		mi, known := t.matIdx[from[i].material]
+		if from[i].material == nil || !known {
+			continue
+		}
+		// (prim only says "a hit" for the hit a bounce left: its material, point and normal are what the weight reads)
+		cfrom[i] = C.rtx_hit{t: C.float(from[i].t), prim: 0, material: mi, point: vec(from[i].point), normal: vec(from[i].normal)}
+	}
+	if rc := C.rtx_trace(scene, inRays, C.uint64_t(len(from)), found, 0, nil); rc != 0 {
+		if gpuMissing(rc) {
+			return nil, errFallback
+		}
+		return nil, rtxErr(rc)
+	}
+	if rc := C.rtx_emitter_weight(scene, inFrom, found, C.uint64_t(len(from)), weights, 0, nil); rc != 0 {
+		return nil, rtxErr(rc)
+	}
+	for i, rec := range unsafe.Slice(weights, len(from)) {
+		var w C.rtx_emitter_weight_record = rec
+		out[i] = EmitterWeight{Weighted: w.flags&C.RTX_EMITTER_WEIGHTED != 0, Weight: float32(w.weight), Geom: float32(w.geom),
+			Light: uint32(w.light)}
+	}
+	return out, nil
+}
+
 // gpuCamera is Camera.init's derived state (camera.go:128-165) as rtx.h's kernel constants.
 func (c *Camera) gpuCamera() C.rtx_camera {
 	return C.rtx_camera{
@@ -849,6 +924,17 @@ func (c *Camera) RenderProgressive(world Hittable, writer io.Writer, passSamples
 // sample by the next-event estimator, in passes of passSamples (<= 0: one pass).  Same mean as Render, another image;
 // a world without emitters gives Render's own image.
 func (c *Camera) RenderDirect(world Hittable, writer io.Writer, passSamples int) error {
+	return c.renderLightSampled(world, writer, passSamples, false)
+}
+
+// RenderMIS is RenderDirect with the light sample and the bounce weighted by the power heuristic (rtx_accum_add_mis,
+// rtx.h "multiple importance sampling of the direct light"): same mean again, and no sample brighter than the
+// emitter, however close a light lies to a surface.
+func (c *Camera) RenderMIS(world Hittable, writer io.Writer, passSamples int) error {
+	return c.renderLightSampled(world, writer, passSamples, true)
+}
+
+func (c *Camera) renderLightSampled(world Hittable, writer io.Writer, passSamples int, mis bool) error {
 	c.init()
 	cfg := c.gpuConfig()
 	if passSamples <= 0 {
@@ -868,7 +954,13 @@ func (c *Camera) RenderDirect(world Hittable, writer io.Writer, passSamples int)
 	defer C.rtx_accum_destroy(acc)
 	for done := 0; done < c.samplesPerPixel; done = int(C.rtx_accum_samples(acc)) {
 		count := min(passSamples, c.samplesPerPixel-done)
-		if rc := C.rtx_accum_add_direct(acc, C.uint32_t(count), nil, 0, nil); rc != 0 {
+		rc := C.int(0)
+		if mis {
+			rc = C.rtx_accum_add_mis(acc, C.uint32_t(count), nil, 0, nil)
+		} else {
+			rc = C.rtx_accum_add_direct(acc, C.uint32_t(count), nil, 0, nil)
+		}
+		if rc != 0 {
 			return rtxErr(rc)
 		}
 	}

@@ -968,8 +968,8 @@ int rtx_scene_lights(const rtx_scene* scene, rtx_light* out, uint32_t cap, uint3
  * that is not SAMPLED has `light` and `rng_draws` filled and every other field zero.
  * The sphere case samples its whole area uniformly: half of the points face away from p, and the shadow ray then
  * finds the sphere's own near side (tmax 0.999 ends before q, tmin 0.001 starts past p).  That is unbiased and
- * wasteful.  Not provided: cone sampling of spheres, power-proportional light selection, multiple importance
- * sampling with the bounce.
+ * wasteful.  Not provided: cone sampling of spheres, power-proportional light selection.  (Multiple importance
+ * sampling with the bounce: the section after this one.)
  * Argument checks (before any device is touched), alignment, n == 0, the scene's mutex, the 32-bit launch cut, the
  * counters and events of its own and the untouched sample scratch are rtx_shade_device's.  Input and output buffers
  * must not overlap. */
@@ -1034,6 +1034,82 @@ int rtx_direct(rtx_scene* scene, uint64_t seed, const rtx_hit* hits, const rtx_p
  * 32), RTX_DIRECT_PRIM_BATCH (lanes a primitive test waits for, 16), RTX_DIRECT_LAUNCH_RECORDS (records per launch of
  * the block: tests of the cut). */
 int rtx_accum_add_direct(rtx_accum* accum, uint32_t count, void* hip_stream, uint32_t flags, rtx_stats* stats);
+
+/* ---- multiple importance sampling of the direct light (ABI 10, additive) ----------------------
+ * The estimator above takes an emitter's radiance after a Lambertian hit from the light sample alone, and a light
+ * sample's g has no bound (a light close to a surface: 1 / d2).  This section weights the two strategies that reach
+ * an emitter point q from a Lambertian hit p, the light sample and the bounce, by the power heuristic (beta = 2).
+ * Nothing of the sections above changes: rtx_direct*, rtx_accum_add_direct and their images are what they were.
+ *
+ * Weighting.  Both densities on the area measure at q: the light sample's is 1 / (L * A_j); the bounce's, whose
+ * direction normal + unit is cosine-distributed, is cs * cl / (PiF32 * d2).  Their ratio, bounce over light, is exactly
+ * the block's g, so the heuristic needs nothing else:
+ *   light sample:                 wl = 1 / (1 + g * g)        g = rtx_direct_sample.geom
+ *   bounce that finds an emitter: wb = 1 - 1 / (1 + g * g)    g evaluated at the point the bounce hit
+ * float32, every operation rounded on its own, no fused multiply-add; a g * g of +inf gives wb = 1 exactly.  The
+ * bounce's g, for a bounce that left the Lambertian hit `from` and found `hit` on a DiffuseLight primitive:
+ *   A    = the emitter table's area of hit.prim, 0 if the table excludes it     L = the table's count
+ *   w    = hit.point - from.point;  d2 = Dot(w, w);  dist = Len(w)
+ *   cs   = Dot(from.normal, w) / dist;  cl = |Dot(hit.normal, w)| / dist
+ *   g    = (((cs * cl) * A) * (float)L) / (PiF32 * d2)
+ * A == 0, d2 == 0 or a NaN g give wb = 1 (and a record's geom = 0): the reference's emission is kept whole.  So an
+ * emitter the table excludes (radius <= 0, zero area) is NOT dropped, which removes the CAVEAT above for this mode.
+ * wl + wb = 1 wherever both strategies can produce q; a light sample adds at most a * Le / 2 (g / (1 + g * g) <= 1/2),
+ * a weighted bounce at most a * Le.  No random number is drawn and no new Philox event range is used.
+ *
+ * The per-primitive lookup the weight reads: entry k < n_spheres is the caller's sphere k, entry n_spheres + k the
+ * caller's quad k; area and light are the emitter table's (bit-equal), 0 and RTX_LIGHT_NONE for every primitive that
+ * is not in it.  Host only, validated as rtx_lights; *n = n_spheres + n_quads, out filled when cap >= *n. */
+typedef struct rtx_prim_light { /* 8 B */
+    float area;
+    uint32_t light; /* index into the emitter table, or RTX_LIGHT_NONE */
+} rtx_prim_light;
+#define RTX_LIGHT_NONE 0xFFFFFFFFu
+int rtx_prim_lights(const rtx_scene_desc* desc, rtx_prim_light* out, uint32_t cap, uint32_t* n_spheres, uint32_t* n);
+
+/* The block.  Record i takes d_from[i], the hit a bounce left, and d_hits[i], the closest hit that bounce found
+ * (both as rtx_trace* wrote them), and gives the bounce's weight.  A record is NOT WEIGHTED (weight = 1, geom = 0,
+ * light = RTX_LIGHT_NONE, flags = 0) when hit is a miss, hit.material is outside the table or no DiffuseLight,
+ * from is a miss, or from.material is outside the table or not Lambertian.  Otherwise light is hit.prim's table index
+ * (RTX_LIGHT_NONE when the table excludes it, or hit.prim names no primitive of the scene) and, when A > 0, d2 > 0
+ * and g is no NaN, RTX_EMITTER_WEIGHTED is set, geom = g and weight = wb; else weight = 1, geom = 0.
+ * Argument checks, alignment, n == 0, the scene's mutex, the launch cut, counters and events are rtx_direct_device's
+ * (RTX_EMITTER_LAUNCH_RECORDS: records per launch, tests of the cut).  No walk, no texture, no random number. */
+typedef struct rtx_emitter_weight_record { /* 16 B */
+    float weight;   /* wb */
+    float geom;     /* g; 0 when not WEIGHTED */
+    uint32_t light; /* table index of hit.prim, or RTX_LIGHT_NONE */
+    uint32_t flags; /* RTX_EMITTER_WEIGHTED */
+} rtx_emitter_weight_record;
+#define RTX_EMITTER_WEIGHTED 1u
+#define RTX_EMITTER_COUNTERS 1u /* counting instantiation: weighted (with stats only) */
+typedef struct rtx_emitter_stats {
+    uint64_t n;        /* records                                                 */
+    uint64_t weighted; /* RTX_EMITTER_COUNTERS: records with RTX_EMITTER_WEIGHTED */
+    double kernel_ms;  /* device time of the launches, HIP events on the stream   */
+} rtx_emitter_stats;
+int rtx_emitter_weight_device(rtx_scene* scene, const rtx_hit* d_from, const rtx_hit* d_hits, uint64_t n,
+                              rtx_emitter_weight_record* d_out, uint32_t flags, void* hip_stream,
+                              rtx_emitter_stats* stats);
+/* The same for records in host memory, on the current device.  Blocking. */
+int rtx_emitter_weight(rtx_scene* scene, const rtx_hit* from, const rtx_hit* hits, uint64_t n,
+                       rtx_emitter_weight_record* out, uint32_t flags, rtx_emitter_stats* stats);
+
+/* The estimator and the fused pass: the rule of rtx_accum_add_direct with two lines changed (`diffuse` as there):
+ *
+ *   hit:   if EMITS:  L += T * (diffuse ? emitted * wb : emitted)        wb of (the previous hit, this hit)
+ *          ...        if d.VISIBLE:  L += T * (d.radiance * wl)          wl of d.geom
+ *
+ * The sample-taking condition and so the set of path lengths are unchanged; wb applies whenever diffuse is set,
+ * whether or not the light sample at the previous hit was SAMPLED.  With no emitter, or at max_depth 1, the result is
+ * the plain render bit for bit.  Unbiased: at every emitter point visible from p the two weights sum to 1, and where
+ * one strategy cannot produce q (a sphere's far side, cs <= 0) neither adds anything.
+ * rtx_accum_add_mis is rtx_accum_add_direct for this estimator, one kernel, equal bit for bit to the composition
+ * rtx_trace -> rtx_shade -> rtx_emitter_weight -> rtx_direct (wavefront.py's render(direct=True, mis=True)) as stated
+ * there.  An accumulator has a fourth mode: rtx_accum_add_mis after a plain, adaptive or direct pass, and any of those
+ * after it, return RTX_ERR_INVALID_ARG until rtx_accum_reset, as do a NULL accumulator, count == 0, n + count past
+ * 2^32 - 1 and flags != 0, all before any device is touched.  Stats, readers and knobs are rtx_accum_add_direct's. */
+int rtx_accum_add_mis(rtx_accum* accum, uint32_t count, void* hip_stream, uint32_t flags, rtx_stats* stats);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,7 @@ struct rtx_accum {
     rtxd::DeviceBuffer adapt;
     bool adaptive = false;  // an adaptive pass since create / reset: the tiles no longer share one n
     bool direct = false;    // a direct-light pass since create / reset: another estimator's samples
+    bool mis = false;       // an MIS pass since create / reset: a third estimator's
     uint32_t n = 0;         // the frontier: the samples offered so far
     float* s() const { return sums.as<float>(); }
     float* q() const { return s() + slots * 3; }
@@ -146,6 +147,7 @@ int rtx_accum_add(rtx_accum* a, uint32_t count, void* hip_stream, uint32_t flags
     if (a->adaptive)
         return fail(RTX_ERR_INVALID_ARG, "a uniform pass after an adaptive one: the tiles no longer share one n (reset first)");
     if (a->direct) return fail(RTX_ERR_INVALID_ARG, "a plain pass after a direct-light one: another estimator (reset first)");
+    if (a->mis) return fail(RTX_ERR_INVALID_ARG, "a plain pass after an MIS one: another estimator (reset first)");
     if (int rc = accum_device(a)) return rc;
     rtx_scene* s = a->scene;
     std::lock_guard<std::mutex> lk(s->mu);
@@ -172,6 +174,7 @@ int rtx_accum_add_adaptive(rtx_accum* a, uint32_t count, float rel_tol, uint32_t
     if (int rc = check_sample_range(a->n, count)) return rc;
     if (!(rel_tol >= 0.0f)) return fail(RTX_ERR_INVALID_ARG, "rel_tol %g: a tolerance is >= 0", (double)rel_tol);
     if (a->direct) return fail(RTX_ERR_INVALID_ARG, "an adaptive pass after a direct-light one: another estimator (reset first)");
+    if (a->mis) return fail(RTX_ERR_INVALID_ARG, "an adaptive pass after an MIS one: another estimator (reset first)");
     if (int rc = accum_device(a)) return rc;
     rtx_scene* s = a->scene;
     hipStream_t st = (hipStream_t)hip_stream;
@@ -216,15 +219,19 @@ int rtx_accum_add_adaptive(rtx_accum* a, uint32_t count, float rel_tol, uint32_t
     return rc;
 }
 
-int rtx_accum_add_direct(rtx_accum* a, uint32_t count, void* hip_stream, uint32_t flags, rtx_stats* stats) {
-    g_last_error.clear();
+namespace {
+// rtx_accum_add_direct and rtx_accum_add_mis: one fused pass of the estimator `mis` names, after the checks that need no
+// device.  The accumulator's first pass, or one more of the same estimator.
+int add_light_pass(rtx_accum* a, uint32_t count, void* hip_stream, uint32_t flags, rtx_stats* stats, bool mis) {
+    const char* what = mis ? "an MIS" : "a direct-light";
     if (!a) return fail(RTX_ERR_INVALID_ARG, "NULL accumulator");
     if (count == 0) return fail(RTX_ERR_INVALID_ARG, "a pass of 0 samples");
     if (int rc = check_sample_range(a->n, count)) return rc;
-    if (flags != 0u) return fail(RTX_ERR_INVALID_ARG, "direct pass flags 0x%x: must be 0", flags);
-    if (a->adaptive) return fail(RTX_ERR_INVALID_ARG, "a direct-light pass after an adaptive one (reset first)");
-    if (a->n != 0u && !a->direct)
-        return fail(RTX_ERR_INVALID_ARG, "a direct-light pass after a plain one: another estimator (reset first)");
+    if (flags != 0u) return fail(RTX_ERR_INVALID_ARG, "%s pass flags 0x%x: must be 0", mis ? "MIS" : "direct", flags);
+    if (a->adaptive) return fail(RTX_ERR_INVALID_ARG, "%s pass after an adaptive one (reset first)", what);
+    if (a->n != 0u && !(mis ? a->mis : a->direct))
+        return fail(RTX_ERR_INVALID_ARG, "%s pass after %s one: another estimator (reset first)", what,
+                    a->direct ? "a direct-light" : a->mis ? "an MIS" : "a plain");
     if (int rc = accum_device(a)) return rc;
     rtx_scene* s = a->scene;
     std::lock_guard<std::mutex> lk(s->mu);
@@ -232,14 +239,25 @@ int rtx_accum_add_direct(rtx_accum* a, uint32_t count, void* hip_stream, uint32_
     if (int rc = ensure_device(s, a->device, &c)) return rc;
     if (a->slots != 0) {  // (an empty shard: nothing to render)
         if (int rc = direct_pass_locked(s, &a->cam, a->seed, &a->region, a->tile_w_log2, a->n, count, a->s(), a->q(),
-                                        (hipStream_t)hip_stream, stats))
+                                        (hipStream_t)hip_stream, stats, mis))
             return rc;
     } else if (stats) {
         *stats = rtx_stats{};
     }
-    a->direct = true;
+    (mis ? a->mis : a->direct) = true;
     a->n += count;
     return RTX_OK;
+}
+}  // namespace
+
+int rtx_accum_add_direct(rtx_accum* a, uint32_t count, void* hip_stream, uint32_t flags, rtx_stats* stats) {
+    g_last_error.clear();
+    return add_light_pass(a, count, hip_stream, flags, stats, false);
+}
+
+int rtx_accum_add_mis(rtx_accum* a, uint32_t count, void* hip_stream, uint32_t flags, rtx_stats* stats) {
+    g_last_error.clear();
+    return add_light_pass(a, count, hip_stream, flags, stats, true);
 }
 
 uint32_t rtx_accum_samples(const rtx_accum* a) { return a ? a->n : 0u; }
@@ -403,6 +421,7 @@ int rtx_accum_reset(rtx_accum* a) {
     HIP_TRY(hipMemset(a->adapt.ptr, 0, a->adapt.bytes));  // every tile open again
     a->adaptive = false;
     a->direct = false;
+    a->mis = false;
     a->n = 0;
     return RTX_OK;
 }

@@ -37,6 +37,13 @@ struct DirectParams {
 // Perlin texture.
 hipError_t launch_direct(const DirectParams& p, bool count, bool noise, hipStream_t stream);
 
+// The per-primitive lookup of rtx_prim_lights on the device (build_lights, rtx_scene.hip): (area, light index) of the
+// caller's sphere k at [k], k < n_spheres, and of its quad k at [n_spheres + k], k < n_quads.
+struct PrimLights {
+    const float2* tab;
+    uint32_t n_spheres, n_quads;
+};
+
 // One launch of the fused pass (rtx_accum_add_direct, direct_paths): samples [k0, k0 + kn) of the region's
 // width * rows pixels (at most 2^32 - 1) by the estimator of DESIGN.md §37, folded into the accumulator's tile-major
 // moments acc_s and acc_q (slot = tile * 64 + lane, 3 floats each; rtx_kernel.hip accumulate_samples' layout).
@@ -55,7 +62,26 @@ struct DirectPathParams {
     const float4* lights;
     float* acc_s;
     float* acc_q;
+    // the MIS instantiations alone (rtx_accum_add_mis)
+    const uint32_t* rank_sphere;  // rank word of a sphere entry -> the caller's sphere index (rtx_trace.h)
+    PrimLights prims;
 };
-// Enqueue one launch on `stream`.  noise: the scene has a Perlin texture.
-hipError_t launch_direct_paths(const DirectPathParams& p, bool noise, hipStream_t stream);
+// Enqueue one launch on `stream`.  noise: the scene has a Perlin texture.  mis: the estimator of rtx_accum_add_mis.
+hipError_t launch_direct_paths(const DirectPathParams& p, bool noise, bool mis, hipStream_t stream);
+
+// One launch of the emitter-weight block (rtx_emitter_weight_device, emitter_weights): records [0, n) of the three
+// arrays, n <= DIRECT_LAUNCH_MAX.
+constexpr uint32_t EMITTER_WEIGHTED = 0u;  // its counter's slot (the direct block's Probe)
+struct EmitterWeightParams {
+    const rtx_material* materials;
+    uint32_t n_materials;
+    uint32_t n_lights;  // L
+    PrimLights prims;
+    const rtx_hit* from;
+    const rtx_hit* hits;
+    rtx_emitter_weight_record* out;
+    uint32_t n;
+    unsigned long long* counters;  // the counting instantiation
+};
+hipError_t launch_emitter_weights(const EmitterWeightParams& p, bool count, hipStream_t stream);
 }  // namespace rtxd

@@ -116,6 +116,72 @@ __device__ __forceinline__ LightSample light_sample(const LightTables& p, const 
     return s;
 }
 
+// ---- multiple importance sampling (rtx.h, "multiple importance sampling of the direct light") ------
+// (area, light index) of rtx_hit's prim word in the per-primitive lookup; a word that names no primitive of the
+// scene (a miss, a caller's own record) is no emitter.
+__device__ __forceinline__ float2 prim_light(const PrimLights& t, const uint32_t prim) {
+    const uint32_t kind = prim >> 28, idx = prim & 0x0FFFFFFFu;
+    const bool sph = kind == RTX_PRIM_SPHERE && idx < t.n_spheres, quad = kind == RTX_PRIM_QUAD && idx < t.n_quads;
+    if (!sph && !quad) return make_float2(0.0f, __uint_as_float(RTX_LIGHT_NONE));
+    return t.tab[sph ? idx : t.n_spheres + idx];
+}
+
+// The weight of a bounce that left the Lambertian hit (from_pt, from_n) and found (hit_pt, hit_n) on an emitter of
+// area `area` (0: the table excludes it): the contract's g and wb = 1 - 1 / (1 + g * g), each operation rounded.
+struct BounceWeight {
+    bool weighted;
+    float wb, g;
+};
+__device__ __forceinline__ BounceWeight bounce_weight(const float area, const float fL, const V3 from_pt, const V3 from_n,
+                                                      const V3 hit_pt, const V3 hit_n) {
+    const float pi32 = 3.14159274101257324f;  // PiF32, math.go:48
+    const V3 w = sub(hit_pt, from_pt);
+    const float d2 = dot(w, w);
+    const float dist = (float)__builtin_sqrt((double)d2);  // vec3.go:119-121
+    const float cs = dot(from_n, w) / dist;
+    const float cl = __builtin_fabsf(dot(hit_n, w)) / dist;
+    const float g = (((cs * cl) * area) * fL) / (pi32 * d2);
+    const bool ok = area > 0.0f && d2 > 0.0f && g == g;  // (a NaN fails)
+    const float wb = 1.0f - 1.0f / (1.0f + g * g);
+    return BounceWeight{ok, ok ? wb : 1.0f, ok ? g : 0.0f};
+}
+
+// The light sample's weight of its own g.
+__device__ __forceinline__ float light_weight(const float g) { return 1.0f / (1.0f + g * g); }
+
+// rtx_emitter_weight_device: a thread per record, 64 records per wave step, no walk and no cross-lane state but the
+// counting instantiation's sum (every lane of a launched wave reaches it).
+template <bool COUNT>
+__global__ __launch_bounds__(256) void emitter_weights(EmitterWeightParams p) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool live = i < p.n;
+    const uint32_t rec = live ? i : p.n - 1u;
+    // 2 x 48 B in: 3 + 3 dwordx4 loads
+    const float4* fp = reinterpret_cast<const float4*>(p.from + rec);
+    const float4* hp = reinterpret_cast<const float4*>(p.hits + rec);
+    const float4 f0 = fp[0], f1 = fp[1], f2 = fp[2], h0 = hp[0], h1 = hp[1], h2 = hp[2];
+    const uint32_t fm = __float_as_uint(f0.z), hm = __float_as_uint(h0.z), prim = __float_as_uint(h0.y);
+    // (a material index outside the table is no hit: the records come from the caller)
+    const bool from_ok = __float_as_uint(f0.y) != RTX_HIT_NONE && fm < p.n_materials;
+    const bool hit_ok = prim != RTX_HIT_NONE && hm < p.n_materials;
+    const float4 fm0 = *reinterpret_cast<const float4*>(p.materials + (from_ok ? fm : 0u));  // the device form: type in .x
+    const float4 hm0 = *reinterpret_cast<const float4*>(p.materials + (hit_ok ? hm : 0u));
+    const bool pair = from_ok && hit_ok && __float_as_uint(fm0.x) == RTX_MAT_LAMBERTIAN &&
+                      __float_as_uint(hm0.x) == RTX_MAT_DIFFUSE_LIGHT;
+    float2 pl = make_float2(0.0f, __uint_as_float(RTX_LIGHT_NONE));
+    if (pair) pl = prim_light(p.prims, prim);
+    const BounceWeight bw = bounce_weight(pl.x, (float)p.n_lights, v3(f1.x, f1.y, f1.z), v3(f2.x, f2.y, f2.z),
+                                          v3(h1.x, h1.y, h1.z), v3(h2.x, h2.y, h2.z));
+    const bool weighted = pair && bw.weighted;
+    if (live)  // 16 B out: one dwordx4 store
+        *reinterpret_cast<float4*>(p.out + i) = make_float4(weighted ? bw.wb : 1.0f, weighted ? bw.g : 0.0f, pl.y,
+                                                            __uint_as_float(weighted ? RTX_EMITTER_WEIGHTED : 0u));
+    if (COUNT) {
+        const uint32_t nw = wave_sum(live && weighted ? 1u : 0u);
+        if ((threadIdx.x & 63u) == 0u && nw) atomicAdd(&p.counters[EMITTER_WEIGHTED], (unsigned long long)nw);
+    }
+}
+
 // COUNT: the counting instantiation (sampled, visible, rng_draws).  QUADS: the scene holds quads.  FIXED: the scene
 // in the workgroup's LDS copy (scene_ref_fixed), else read from HBM.  NOISE: the scene has a Perlin texture.
 template <bool COUNT, bool QUADS, bool FIXED, bool NOISE>
@@ -208,8 +274,11 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void direct_lights(DirectParams p)
 // segments and walk positions only move forward); every vote (here, in trav_begin, unit, the batched step) sits where
 // the whole wave arrives, except those inside a lane's own material branch, as in shade_hits.
 // QUADS: the scene holds quads.  FIXED: the scene in the workgroup's LDS copy, else read from HBM.  NOISE: the scene has
-// a Perlin texture.
-template <bool QUADS, bool FIXED, bool NOISE>
+// a Perlin texture.  MIS: the estimator of rtx_accum_add_mis: the lane also keeps the normal of the
+// Lambertian hit its bounce left (r.o is that hit's point), a bounce that finds an emitter is weighted by bounce_weight
+// of the per-primitive lookup, a light sample by light_weight of its g.  Every MIS line is under `if (MIS)`: the
+// MIS = false instantiations are what they were.
+template <bool QUADS, bool FIXED, bool NOISE, bool MIS>
 __global__ __launch_bounds__(64 * WALK_WAVES) void direct_paths(DirectPathParams p) {
     extern __shared__ float4 lds_entries[];
     const SceneRef E = stage_scene<WALK_WAVES, FIXED>(lds_entries, p.scene);
@@ -234,6 +303,7 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void direct_paths(DirectPathParams
     const uint32_t kend = sh.k0 + sh.kn;  // (at most 2^32 - 1: the entry's check)
     uint32_t seg = 0, cam_draws = 0;
     bool shadow = false, diffuse = false;
+    V3 from_n = zero;  // MIS: the normal of the Lambertian hit the walking bounce left
     V3 T = one, Lc = zero, pending = zero, bounce = zero;  // pending: T * radiance of the walking shadow ray; bounce: the saved direction
     // the lane's slot of the tile-major moments: the pass continues the sums in k order (passes of one accumulator
     // are ordered by the caller), so they are read here and written back at the end
@@ -261,7 +331,7 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void direct_paths(DirectPathParams
             // -- the fold step, whole wave.  What follows is computed by every lane on its own walk and kept where
             //    `seg_end` (a parked closest walk) or `sh_end` (a parked shadow walk) says so.
             const bool seg_end = pend && !shadow, sh_end = pend && shadow;
-            const HitRecord h = hit_record<QUADS>(E, t, r, want_uv);
+            const HitRecord h = hit_record<QUADS, MIS>(E, t, r, want_uv, p.rank_sphere);
             const bool hit = seg_end && h.hit && h.mi < p.n_materials;
             const float4* mp = reinterpret_cast<const float4*>(p.materials + (hit ? h.mi : 0u));
             const float4 m0 = mp[0], m1 = mp[1];
@@ -336,12 +406,18 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void direct_paths(DirectPathParams
                     sample_done = true;
                 } else {
                     if (emits && !diffuse) Lc = add(Lc, mul(T, em));    // ray.go:41, 47
-                    if (ls.sampled) pending = mul(T, ls.rad);
+                    if (MIS && emits && diffuse) {                      // the bounce's share of this emitter point
+                        const float area = prim_light(p.prims, h.prim).x;
+                        const BounceWeight bw = bounce_weight(area, (float)p.n_lights, r.o, from_n, h.pt, h.n);
+                        Lc = add(Lc, mul(T, scale(em, bw.wb)));
+                    }
+                    if (ls.sampled) pending = MIS ? mul(T, scale(ls.rad, light_weight(ls.g))) : mul(T, ls.rad);
                     if (!scattered) {
                         sample_done = true;
                     } else {
                         T = mul(T, att);                                // ray.go:47-50
                         diffuse = lam && p.n_lights != 0u;
+                        if (MIS && lam) from_n = h.n;
                         ++seg;
                         if (seg >= depth) {
                             sample_done = true;                         // the depth cap: nothing more is added
@@ -411,12 +487,17 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void direct_paths(DirectPathParams
 }
 
 template <bool QUADS, bool FIXED>
-hipError_t launch_paths_noise(const DirectPathParams& p, bool noise, hipStream_t stream) {
+hipError_t launch_paths_noise(const DirectPathParams& p, bool noise, bool mis, hipStream_t stream) {
     const size_t shmem = FIXED ? walk_lds_bytes(p.scene.n_entries, p.scene.n_quads) : 0;
     const uint64_t tiles = (uint64_t)tiles_x_of(p.shard.width, p.tile_w_log2) * tiles_y_of(p.shard.rows, p.tile_w_log2);
     const dim3 grid((uint32_t)((tiles + WALK_WAVES - 1) / WALK_WAVES)), block(64 * WALK_WAVES);
-    if (noise) hipLaunchKernelGGL((direct_paths<QUADS, FIXED, true>), grid, block, shmem, stream, p);
-    else hipLaunchKernelGGL((direct_paths<QUADS, FIXED, false>), grid, block, shmem, stream, p);
+    if (mis) {
+        if (noise) hipLaunchKernelGGL((direct_paths<QUADS, FIXED, true, true>), grid, block, shmem, stream, p);
+        else hipLaunchKernelGGL((direct_paths<QUADS, FIXED, false, true>), grid, block, shmem, stream, p);
+    } else {
+        if (noise) hipLaunchKernelGGL((direct_paths<QUADS, FIXED, true, false>), grid, block, shmem, stream, p);
+        else hipLaunchKernelGGL((direct_paths<QUADS, FIXED, false, false>), grid, block, shmem, stream, p);
+    }
     return hipGetLastError();
 }
 
@@ -448,17 +529,29 @@ hipError_t launch_direct(const DirectParams& p, bool count, bool noise, hipStrea
     return count ? launch_count<true>(p, noise, stream) : launch_count<false>(p, noise, stream);
 }
 
-hipError_t launch_direct_paths(const DirectPathParams& p, bool noise, hipStream_t stream) {
+hipError_t launch_emitter_weights(const EmitterWeightParams& p, bool count, hipStream_t stream) {
+    if (p.n == 0) return hipSuccess;
+    if (p.n > DIRECT_LAUNCH_MAX || !p.from || !p.hits || !p.out || !p.materials || !p.prims.tab || p.n_lights > (1u << 24) ||
+        (count && !p.counters))
+        return hipErrorInvalidValue;
+    const dim3 grid((p.n + 255u) / 256u), block(256);
+    if (count) hipLaunchKernelGGL(emitter_weights<true>, grid, block, 0, stream, p);
+    else hipLaunchKernelGGL(emitter_weights<false>, grid, block, 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_direct_paths(const DirectPathParams& p, bool noise, bool mis, hipStream_t stream) {
     const Shard& sh = p.shard;
     const uint64_t P = (uint64_t)sh.width * sh.rows;
     if (P == 0 || sh.kn == 0) return hipSuccess;
     if (P > 0xFFFFFFFFull || (uint64_t)sh.k0 + sh.kn > 0xFFFFFFFFull || p.tile_w_log2 > 6u || p.refill == 0 || p.refill > 64u ||
         sh.world == 0 || sh.rank >= sh.world || !p.scene.entries || !p.materials || !p.textures || !p.texels || !p.acc_s || !p.acc_q ||
-        (p.n_lights && !p.lights) || p.n_lights > (1u << 24))
+        (p.n_lights && !p.lights) || p.n_lights > (1u << 24) || (mis && (!p.rank_sphere || !p.prims.tab)))
         return hipErrorInvalidValue;
     const bool fixed = trace_placement(p.scene.n_entries, p.scene.n_quads) == RTX_SCENE_IN_LDS;
-    if (p.scene.n_quads) return fixed ? launch_paths_noise<true, true>(p, noise, stream) : launch_paths_noise<true, false>(p, noise, stream);
-    return fixed ? launch_paths_noise<false, true>(p, noise, stream) : launch_paths_noise<false, false>(p, noise, stream);
+    if (p.scene.n_quads)
+        return fixed ? launch_paths_noise<true, true>(p, noise, mis, stream) : launch_paths_noise<true, false>(p, noise, mis, stream);
+    return fixed ? launch_paths_noise<false, true>(p, noise, mis, stream) : launch_paths_noise<false, false>(p, noise, mis, stream);
 }
 
 }  // namespace rtxd

@@ -65,6 +65,7 @@ struct rtx_scene {
     bool lights_built = false;
     std::vector<rtx_light> lights;
     std::vector<float> lighttab;
+    std::vector<rtx_prim_light> primlights;  // rtx_prim_lights' lookup: sphere_rank.size() spheres, then the quads
     std::mutex mu;
 };
 
@@ -92,9 +93,11 @@ uint32_t region_rows(const rtx_region* r);
 uint32_t band_stripe(int n);
 // The emitter table of a scene's entries in the reference walk's order (`base`), its quad table and its materials
 // (rtx.h, "direct light sampling"): `lights` in table order and, when tab != nullptr, 16 floats per emitter for the
-// device: (centre | Q, radius | 0), (u, area), (v, kind: RTX_PRIM_*), (the quad's normal, material).
+// device: (centre | Q, radius | 0), (u, area), (v, kind: RTX_PRIM_*), (the quad's normal, material).  prims != nullptr:
+// also the per-primitive lookup of rtx_prim_lights, n_spheres entries for the caller's spheres, then one per quad.
 int build_lights(const std::vector<rtx_entry>& base, const std::vector<float>& quadtab,
-                 const std::vector<rtx_material>& materials, std::vector<rtx_light>& lights, std::vector<float>* tab);
+                 const std::vector<rtx_material>& materials, std::vector<rtx_light>& lights, std::vector<float>* tab,
+                 std::vector<rtx_prim_light>* prims = nullptr, uint32_t n_spheres = 0);
 // The scene's own table, built on first use (s->mu held).
 int scene_lights(rtx_scene* s);
 
@@ -173,6 +176,7 @@ struct DeviceCopy {
     DeviceLayout trace_lay[8];
     DeviceBuffer rank_sphere;  // rank word of a sphere entry -> the caller's sphere index (first trace)
     DeviceBuffer lights;       // direct light sampling: the emitter records (first call)
+    DeviceBuffer prim_lights;  // multiple importance sampling: the per-primitive lookup, with `lights`
     // ray queries (and the guide images' timing), path building blocks, direct light sampling
     Probe trace, shade, direct;
 
@@ -306,8 +310,10 @@ int guides_locked(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const rtx_
 
 // ---- rtx_direct_capi.hip -------------------------------------------------------------------------------------
 // One fused direct-light pass into an accumulator's moments (rtx_accum_add_direct after its checks), s->mu held.
+// mis: the estimator of rtx_accum_add_mis.
 int direct_pass_locked(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const rtx_region* region, uint32_t tile_w_log2,
-                       uint32_t first, uint32_t count, float* acc_s, float* acc_q, hipStream_t stream, rtx_stats* stats);
+                       uint32_t first, uint32_t count, float* acc_s, float* acc_q, hipStream_t stream, rtx_stats* stats,
+                       bool mis = false);
 
 // ---- rtx_bands.hip -------------------------------------------------------------------------------------------
 int render_bands_locked(rtx_scene* s, const rtx_camera* cam, uint64_t seed, int n_gpus, uint32_t flags, float* out_rgb,

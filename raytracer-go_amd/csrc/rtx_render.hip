@@ -70,7 +70,7 @@ void free_copy(DeviceCopy& c) {
     (void)hipDeviceSynchronize();  // no render of this copy still running
     for (DeviceLayout& l : c.lay) l.entries.release();
     for (DeviceLayout& l : c.trace_lay) l.entries.release();
-    for (DeviceBuffer* b : {&c.rank_sphere, &c.lights, &c.materials, &c.textures, &c.texels, &c.counters}) b->release();
+    for (DeviceBuffer* b : {&c.rank_sphere, &c.lights, &c.prim_lights, &c.materials, &c.textures, &c.texels, &c.counters}) b->release();
     for (Probe* p : {&c.trace, &c.shade, &c.direct}) p->release();
     for (hipEvent_t ev : {c.ev0, c.ev1})
         if (ev) (void)hipEventDestroy(ev);

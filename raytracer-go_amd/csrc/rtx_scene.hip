@@ -232,7 +232,8 @@ void quad_table(const rtx_scene_desc* d, std::vector<float>& tab) {
 // entries name and whose material is a DiffuseLight, each once, in table order.  Every float operation is float32 and
 // rounded on its own (the unit is built without contraction): area = (4 * PiF32) * (r * r), or Len(Cross(u, v)).
 int build_lights(const std::vector<rtx_entry>& base, const std::vector<float>& quadtab,
-                 const std::vector<rtx_material>& materials, std::vector<rtx_light>& lights, std::vector<float>* tab) {
+                 const std::vector<rtx_material>& materials, std::vector<rtx_light>& lights, std::vector<float>* tab,
+                 std::vector<rtx_prim_light>* prims, uint32_t n_spheres) {
     struct Emitter {
         uint32_t index, material;
         float a[4], u[3], v[3], n[3];  // a: (centre, radius) or (Q, 0)
@@ -267,8 +268,12 @@ int build_lights(const std::vector<rtx_entry>& base, const std::vector<float>& q
     }
     lights.clear();
     if (tab) tab->clear();
+    // the per-primitive lookup (rtx.h, "multiple importance sampling"): the caller's spheres, then its quads
+    if (prims) prims->assign((size_t)n_spheres + quadtab.size() / 16, rtx_prim_light{0.0f, RTX_LIGHT_NONE});
     const auto put = [&](const Emitter& m, uint32_t kind, float area) {
         if (!(std::isfinite(area) && area > 0.0f)) return;
+        const size_t slot = kind == RTX_PRIM_QUAD ? (size_t)n_spheres + m.index : (size_t)m.index;
+        if (prims && (kind == RTX_PRIM_QUAD || m.index < n_spheres)) (*prims)[slot] = rtx_prim_light{area, (uint32_t)lights.size()};
         lights.push_back(rtx_light{(kind << 28) | m.index, area});
         if (!tab) return;
         float rec[16] = {m.a[0], m.a[1], m.a[2], m.a[3], m.u[0], m.u[1], m.u[2], area,
@@ -293,6 +298,7 @@ int build_lights(const std::vector<rtx_entry>& base, const std::vector<float>& q
         const size_t L = lights.size();
         lights.clear();
         if (tab) tab->clear();
+        if (prims) prims->clear();
         return fail(RTX_ERR_INVALID_ARG, "%zu emitters: more than 2^24 (the light index is drawn from one float32)", L);
     }
     return RTX_OK;
@@ -300,7 +306,9 @@ int build_lights(const std::vector<rtx_entry>& base, const std::vector<float>& q
 
 int scene_lights(rtx_scene* s) {
     if (s->lights_built) return RTX_OK;
-    if (int rc = build_lights(s->base, s->quadtab, s->materials, s->lights, &s->lighttab)) return rc;
+    if (int rc = build_lights(s->base, s->quadtab, s->materials, s->lights, &s->lighttab, &s->primlights,
+                              (uint32_t)s->sphere_rank.size()))
+        return rc;
     s->lights_built = true;
     return RTX_OK;
 }
@@ -792,20 +800,40 @@ int copy_lights(const std::vector<rtx_light>& v, rtx_light* out, uint32_t cap, u
 }
 }  // namespace
 
-int rtx_lights(const rtx_scene_desc* d, rtx_light* out, uint32_t cap, uint32_t* n) {
-    g_last_error.clear();
-    if (!d || !n) return fail(RTX_ERR_INVALID_ARG, "bad argument");
-    *n = 0;
+namespace {
+// The emitter table of a description and, when prims != nullptr, its per-primitive lookup (rtx_lights, rtx_prim_lights).
+int desc_lights(const rtx_scene_desc* d, std::vector<rtx_light>& lights, std::vector<rtx_prim_light>* prims) {
     if (d->n_lists && !d->lists) return fail(RTX_ERR_INVALID_ARG, "lists is NULL");
     if (d->n_list_refs && !d->list_refs) return fail(RTX_ERR_INVALID_ARG, "list_refs is NULL");
     std::vector<rtx_entry> base;
     if (int rc = flatten(d, base)) return rc;
     std::vector<float> quadtab;
     quad_table(d, quadtab);
+    return build_lights(base, quadtab, std::vector<rtx_material>(d->materials, d->materials + d->n_materials), lights, nullptr,
+                        prims, d->n_spheres);
+}
+}  // namespace
+
+int rtx_lights(const rtx_scene_desc* d, rtx_light* out, uint32_t cap, uint32_t* n) {
+    g_last_error.clear();
+    if (!d || !n) return fail(RTX_ERR_INVALID_ARG, "bad argument");
+    *n = 0;
     std::vector<rtx_light> lights;
-    if (int rc = build_lights(base, quadtab, std::vector<rtx_material>(d->materials, d->materials + d->n_materials), lights, nullptr))
-        return rc;
+    if (int rc = desc_lights(d, lights, nullptr)) return rc;
     return copy_lights(lights, out, cap, n);
+}
+
+int rtx_prim_lights(const rtx_scene_desc* d, rtx_prim_light* out, uint32_t cap, uint32_t* n_spheres, uint32_t* n) {
+    g_last_error.clear();
+    if (!d || !n || !n_spheres) return fail(RTX_ERR_INVALID_ARG, "bad argument");
+    *n = *n_spheres = 0;
+    std::vector<rtx_light> lights;
+    std::vector<rtx_prim_light> prims;
+    if (int rc = desc_lights(d, lights, &prims)) return rc;
+    *n_spheres = d->n_spheres;
+    *n = (uint32_t)prims.size();
+    if (out && cap >= prims.size() && !prims.empty()) std::memcpy(out, prims.data(), prims.size() * sizeof(rtx_prim_light));
+    return RTX_OK;
 }
 
 int rtx_scene_lights(const rtx_scene* scene, rtx_light* out, uint32_t cap, uint32_t* n) {

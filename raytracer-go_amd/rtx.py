@@ -49,6 +49,9 @@ RTX_BOUNCE_EMITS = 2  # Bounce.flags: the material is a DiffuseLight; emitted is
 RTX_SHADE_COUNTERS = 1  # the counting instantiation (with stats)
 RTX_DIRECT_SAMPLED = 1  # DirectSample.flags: a light point was sampled; radiance, ray and geom are its
 RTX_DIRECT_VISIBLE = 2  # DirectSample.flags: the shadow ray met no primitive
+RTX_LIGHT_NONE = 0xFFFFFFFF  # PrimLight.light / EmitterWeight.light: not in the emitter table
+RTX_EMITTER_WEIGHTED = 1  # EmitterWeight.flags: the power heuristic's weight (else weight = 1, geom = 0)
+RTX_EMITTER_COUNTERS = 1  # rtx_emitter_weight* flag: count the weighted records (with stats)
 RTX_DIRECT_COUNTERS = 1  # the counting instantiation (with stats)
 
 
@@ -187,6 +190,18 @@ class DirectStats(ctypes.Structure):  # rtx_direct_stats
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PrimLight(ctypes.Structure):  # rtx_prim_light, 8 B
+    _fields_ = [("area", c_float), ("light", c_uint32)]
+
+
+class EmitterWeight(ctypes.Structure):  # rtx_emitter_weight_record, 16 B
+    _fields_ = [("weight", c_float), ("geom", c_float), ("light", c_uint32), ("flags", c_uint32)]
+
+
+class EmitterStats(ctypes.Structure):  # rtx_emitter_stats
+    _fields_ = [("n", c_uint64), ("weighted", c_uint64), ("kernel_ms", c_double)]
+
+
 class Guide(ctypes.Structure):  # rtx_guide, 32 B
     _fields_ = [("albedo", c_float * 3), ("cover", c_float), ("normal", c_float * 3), ("depth", c_float)]
 
@@ -217,9 +232,16 @@ class DenoiseParams(ctypes.Structure):  # rtx_denoise_params; DenoiseParams.defa
 
 
 def __getattr__(name: str):
-    """RAY_DTYPE / HIT_DTYPE / KEY_DTYPE / BOUNCE_DTYPE / GUIDE_DTYPE / LIGHT_DTYPE / DIRECT_DTYPE: the numpy structured
-    dtypes of rtx_ray, rtx_hit, rtx_path_key, rtx_bounce, rtx_guide, rtx_light and rtx_direct_sample (numpy is imported on
-    first use, as everywhere in this module)."""
+    """RAY_DTYPE / HIT_DTYPE / KEY_DTYPE / BOUNCE_DTYPE / GUIDE_DTYPE / LIGHT_DTYPE / DIRECT_DTYPE / PRIM_LIGHT_DTYPE /
+    EMITTER_WEIGHT_DTYPE: the numpy structured dtypes of rtx_ray, rtx_hit, rtx_path_key, rtx_bounce, rtx_guide, rtx_light,
+    rtx_direct_sample, rtx_prim_light and rtx_emitter_weight_record (numpy is imported on first use, as everywhere in
+    this module)."""
+    if name in ("PRIM_LIGHT_DTYPE", "EMITTER_WEIGHT_DTYPE"):
+        import numpy as np
+        globals().update(PRIM_LIGHT_DTYPE=np.dtype([("area", "<f4"), ("light", "<u4")]),
+                         EMITTER_WEIGHT_DTYPE=np.dtype([("weight", "<f4"), ("geom", "<f4"), ("light", "<u4"),
+                                                        ("flags", "<u4")]))
+        return globals()[name]
     if name == "GUIDE_DTYPE":
         import numpy as np
         globals().update(GUIDE_DTYPE=np.dtype([("albedo", "<f4", (3,)), ("cover", "<f4"), ("normal", "<f4", (3,)),
@@ -267,6 +289,8 @@ RTX_SYMBOLS = [
     "rtx_accum_add_adaptive", "rtx_accum_tile_shape", "rtx_accum_sample_counts_device", "rtx_accum_sample_counts",
     # direct light sampling (ABI 10, additive)
     "rtx_lights", "rtx_scene_lights", "rtx_direct_device", "rtx_direct", "rtx_accum_add_direct",
+    # multiple importance sampling of the direct light (ABI 10, additive)
+    "rtx_prim_lights", "rtx_emitter_weight_device", "rtx_emitter_weight", "rtx_accum_add_mis",
 ]
 RTXHOST_SYMBOLS = [
     "rtxhost_build_scene", "rtxhost_scene_free", "rtxhost_scene_desc", "rtxhost_scene_camera",
@@ -441,6 +465,16 @@ def load() -> ctypes.CDLL:
         L.rtx_direct.restype = c_int
         L.rtx_accum_add_direct.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, POINTER(Stats)]
         L.rtx_accum_add_direct.restype = c_int
+    if hasattr(L, "rtx_accum_add_mis"):  # multiple importance sampling (ABI 10, additive)
+        L.rtx_prim_lights.argtypes = [POINTER(SceneDesc), c_void_p, c_uint32, POINTER(c_uint32), POINTER(c_uint32)]
+        L.rtx_prim_lights.restype = c_int
+        L.rtx_emitter_weight_device.argtypes = [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p,
+                                                POINTER(EmitterStats)]
+        L.rtx_emitter_weight_device.restype = c_int
+        L.rtx_emitter_weight.argtypes = [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(EmitterStats)]
+        L.rtx_emitter_weight.restype = c_int
+        L.rtx_accum_add_mis.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, POINTER(Stats)]
+        L.rtx_accum_add_mis.restype = c_int
     _lib = L
     return L
 
@@ -817,6 +851,42 @@ class DeviceScene:
         out = out.reshape(arrs[0].shape)
         return (out, st) if stats else out
 
+    def emitter_weight_device(self, from_ptr: int, hits_ptr: int, n: int, out_ptr: int, flags: int = 0, stream: int = 0,
+                              stats: bool = False):
+        """rtx_emitter_weight_device: n pairs of rtx_hit (the hit a bounce left, the hit it found) -> n
+        rtx_emitter_weight_record at out_ptr, device memory of the current device (16-B aligned).  Enqueues and returns
+        None, or with stats=True waits and returns the EmitterStats (flags | RTX_EMITTER_COUNTERS fills `weighted`)."""
+        st = EmitterStats() if stats else None
+        check(load().rtx_emitter_weight_device(self._h, c_void_p(from_ptr), c_void_p(hits_ptr), n, c_void_p(out_ptr), flags,
+                                               c_void_p(stream), ctypes.byref(st) if st is not None else None),
+              "rtx_emitter_weight_device")
+        return st
+
+    def emitter_weight(self, from_hits, hits, stats: bool = False, flags: int = 0):
+        """rtx_emitter_weight: two numpy arrays of HIT_DTYPE of one shape in, an array of EMITTER_WEIGHT_DTYPE of that
+        shape out (and the EmitterStats with stats=True).  Blocking."""
+        import numpy as np
+        t = __getattr__("HIT_DTYPE")
+        arrs = [np.asarray(a) for a in (from_hits, hits)]
+        for a, what in zip(arrs, ("from_hits", "hits")):
+            if a.dtype != t:
+                raise TypeError(f"{what} must have dtype {t}, not {a.dtype}")
+            if a.shape != arrs[0].shape:
+                raise ValueError("from_hits and hits must have one shape")
+        n = arrs[0].size
+        src = []
+        for a in arrs:  # 16-B aligned copies
+            b = _aligned_empty(n, t)
+            b[...] = a.reshape(-1)
+            src.append(b)
+        out = _aligned_empty(n, __getattr__("EMITTER_WEIGHT_DTYPE"))
+        st = EmitterStats() if stats else None
+        check(load().rtx_emitter_weight(self._h, *[b.ctypes.data_as(c_void_p) for b in src], n,
+                                        out.ctypes.data_as(c_void_p), flags, ctypes.byref(st) if st is not None else None),
+              "rtx_emitter_weight")
+        out = out.reshape(arrs[0].shape)
+        return (out, st) if stats else out
+
     def accumulator(self, cam: Camera, seed: int, region: Region) -> "Accumulator":
         """rtx_accum_create on the current device: progressive passes over `region` (close it before the scene)."""
         return Accumulator(self, cam, seed, region)
@@ -861,6 +931,15 @@ class Accumulator:
         st = Stats() if stats else None
         check(load().rtx_accum_add_direct(self._h, count, c_void_p(stream), flags,
                                           ctypes.byref(st) if st is not None else None), "rtx_accum_add_direct")
+        return st
+
+    def add_mis(self, count: int, stream: int = 0, stats: bool = False, flags: int = 0):
+        """rtx_accum_add_mis: `count` more samples per pixel by the direct-light estimator with the light sample and the
+        bounce weighted by the power heuristic, one fused kernel.  An accumulator is plain, adaptive,
+        direct or MIS until reset().  Returns the pass's Stats with stats=True (which waits), else None."""
+        st = Stats() if stats else None
+        check(load().rtx_accum_add_mis(self._h, count, c_void_p(stream), flags,
+                                       ctypes.byref(st) if st is not None else None), "rtx_accum_add_mis")
         return st
 
     def add_adaptive(self, count: int, rel_tol: float, min_samples: int = 1, stream: int = 0, stats: bool = True,
@@ -991,6 +1070,20 @@ def lights(desc_ptr):
     """rtx_lights: the emitter table of a scene description, an array of LIGHT_DTYPE.  Host only: no scene, no device."""
     L = load()
     return _light_table(lambda out, cap, n: L.rtx_lights(desc_ptr, out, cap, n), "rtx_lights")
+
+
+def prim_lights(desc_ptr):
+    """rtx_prim_lights: (the per-primitive emitter lookup of a scene description, an array of PRIM_LIGHT_DTYPE: the
+    caller's spheres, then its quads; the number of spheres).  Host only: no scene, no device."""
+    import numpy as np
+    L = load()
+    ns, n = c_uint32(), c_uint32()
+    check(L.rtx_prim_lights(desc_ptr, None, 0, ctypes.byref(ns), ctypes.byref(n)), "rtx_prim_lights")
+    out = np.zeros(n.value, __getattr__("PRIM_LIGHT_DTYPE"))
+    if n.value:
+        check(L.rtx_prim_lights(desc_ptr, out.ctypes.data_as(c_void_p), n.value, ctypes.byref(ns), ctypes.byref(n)),
+              "rtx_prim_lights")
+    return out, ns.value
 
 
 def camera_rays_device(cam: Camera, seed: int, region: Region, first: int, count: int, rays_ptr: int, keys_ptr: int = 0,

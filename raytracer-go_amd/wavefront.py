@@ -20,7 +20,7 @@ _MISS = -1  # RTX_HIT_NONE seen through an int32 view
 
 
 def render(dev: "rtx.DeviceScene", cam: "rtx.Camera", seed: int, region: "rtx.Region", compact: bool = False,
-           counters: bool = False, direct: bool = False):
+           counters: bool = False, direct: bool = False, mis: bool = False):
     """The region's shard rendered on the current device: a float32 torch tensor [rows, width, 3] there (on the
     caller's tree every value is the one rtx_render_region_device gives).  compact=True drops ended paths between rounds (torch indexing) instead
     of carrying them as misses.  counters=True also returns the dict of sums {segments, hits, rng_draws,
@@ -30,7 +30,12 @@ def render(dev: "rtx.DeviceScene", cam: "rtx.Camera", seed: int, region: "rtx.Re
     hit of segment s with s + 1 < max_depth one light sample is added when its shadow ray is free, and the radiance
     the bounce after a Lambertian hit would have found by hitting an emitter is left out.  Same mean as the plain
     render, another image; with no emitter in the scene it IS the plain render.  rng_draws then includes the light
-    samples' draws."""
+    samples' draws.
+
+    direct=True, mis=True is the estimator of DESIGN.md §42 (rtx.h, "multiple importance sampling of the direct light"):
+    the light sample is weighted by wl = 1 / (1 + g * g) of its own geom, and the emission a bounce after a Lambertian
+    hit finds is kept, weighted by rtx_emitter_weight_device's wb of (the previous round's hit, this hit).  mis without
+    direct changes nothing."""
     import torch
 
     stream = torch.cuda.current_stream().cuda_stream
@@ -57,6 +62,10 @@ def render(dev: "rtx.DeviceScene", cam: "rtx.Camera", seed: int, region: "rtx.Re
         if n_lights:
             light = torch.empty((n, 16), dtype=torch.float32, device=cuda)  # rtx_direct_sample: 16 words
             diffuse = torch.zeros(n, dtype=torch.bool, device=cuda)          # the last bounce left a Lambertian
+            if mis:
+                prev = hits                                                  # the previous round's hit records
+                weight = torch.empty((n, 4), dtype=torch.float32, device=cuda)  # rtx_emitter_weight_record: 4 words
+                one = torch.ones((), dtype=torch.float32, device=cuda)
         for s in range(cam.max_depth):
             m = rays.shape[0]
             if counters:
@@ -75,6 +84,11 @@ def render(dev: "rtx.DeviceScene", cam: "rtx.Camera", seed: int, region: "rtx.Re
             emits = hit & ((bits & rtx.RTX_BOUNCE_EMITS) != 0)
             alive = hit & ((bits & rtx.RTX_BOUNCE_SCATTERED) != 0)
             if n_lights:
+                if mis and s > 0 and bool(diffuse.any()):  # the bounce's share of the emitter point it found
+                    dev.emitter_weight_device(prev.data_ptr(), hits.data_ptr(), m, weight.data_ptr(), 0, stream)
+                    shared = emits & diffuse
+                    wb = weight[:m, 0]
+                    L[path[shared]] = L[path[shared]] + T[shared] * (b[shared, 4:7] * wb[shared][:, None])
                 emits = emits & ~diffuse  # a light sample at the last hit stood for this radiance
             L[path[miss]] = L[path[miss]] + T[miss] * background          # ray.go:52
             L[path[emits]] = L[path[emits]] + T[emits] * b[emits, 4:7]    # ray.go:41, 47
@@ -90,7 +104,11 @@ def render(dev: "rtx.DeviceScene", cam: "rtx.Camera", seed: int, region: "rtx.Re
                 # the flag of the round before and sets none that is read: the same as `diffuse = lam` every round)
                 diffuse = alive & (words[:, 13] != 0)
                 lit = diffuse & ((words[:, 3] & rtx.RTX_DIRECT_VISIBLE) != 0)
-                L[path[lit]] = L[path[lit]] + T[lit] * d[lit, 0:3]
+                if mis:
+                    g = d[lit, 14]
+                    L[path[lit]] = L[path[lit]] + T[lit] * (d[lit, 0:3] * (one / (one + g * g))[:, None])
+                else:
+                    L[path[lit]] = L[path[lit]] + T[lit] * d[lit, 0:3]
             if compact:
                 if not bool(alive.any()):
                     break
@@ -98,10 +116,14 @@ def render(dev: "rtx.DeviceScene", cam: "rtx.Camera", seed: int, region: "rtx.Re
                 rays, keys, path = b[alive, 8:16].contiguous(), keys[alive].contiguous(), path[alive]
                 if n_lights:
                     diffuse = diffuse[alive]
+                    if mis:
+                        prev = hits[:m][alive].contiguous()
                 alive = torch.ones(rays.shape[0], dtype=torch.bool, device=cuda)
             else:
                 T = torch.where(alive[:, None], T * b[:, 0:3], T)
                 rays = b[:, 8:16].contiguous()  # an ended path's bounce ray is all zero: a miss from now on
+                if n_lights and mis:
+                    prev = hits.clone()
             keys[:, 2] += 1  # the next scatter's event
     # camera.go:254-263: the samples summed in k order, times float32(1 / spp)
     per_sample = L.view(spp, rows * width, 3)
