@@ -20,6 +20,7 @@
 
 #include "rtx_device.h"
 #include "rtx_kernel.h"
+#include "rtx_launch_name.h"
 
 #ifndef RTX_WALK_STEPS  // walk steps per lane between two wave votes
 #define RTX_WALK_STEPS 6
@@ -1197,9 +1198,11 @@ hipError_t launch_items(Params p, bool use_lds, hipStream_t stream, const Sample
         const uint64_t units = tiles * ((p.kn + p.sub - 1) / p.sub);
         uint64_t blocks = (uint64_t)per_cu * cus;
         if (blocks > (units + WAVES - 1) / WAVES) blocks = (units + WAVES - 1) / WAVES;  // no wave starts idle
-        if (p.debug_launch)
+        if (p.debug_launch) {
             fprintf(stderr, "rtx v3: waves/wg %d, wgs/CU %d, CUs %d, grid %llu, sub %u, units %llu, lds %zu B\n", WAVES,
                     per_cu, cus, (unsigned long long)blocks, p.sub, (unsigned long long)units, shmem);
+            print_launch_name((const void*)kern);
+        }
         e = hipMemsetAsync(p.tile_counter, 0, sizeof(uint32_t), stream);  // (the watchdog flag: once per render)
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(block), shmem, stream, p);
@@ -1283,6 +1286,15 @@ hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream, const SampleR
         // that set any); with the drain each workgroup's region is the queue over the near grid (a region that fills
         // sends the rest to the redo pass)
         const bool drain_now = drain && 2 * bn + 2 <= DRAIN_WORDS;
+        if (pn.debug_launch) {  // the kernels this chunk launches
+            if (drain_now) {
+                print_launch_name(kd);
+            } else {
+                print_launch_name((const void*)kn);
+                print_launch_name((const void*)kf);
+            }
+            print_launch_name((const void*)kr);
+        }
         hipLaunchKernelGGL(chunk_start, dim3(1), dim3(256), 0, stream, pn, (uint32_t)(k0 == rg.first));
         if (drain_now) {
             pn.drain_region = pf.drain_region = pn.defer_cap / (uint32_t)bn;
