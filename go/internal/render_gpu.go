@@ -9,8 +9,8 @@
 //   CGO_CFLAGS="-I$RTX/include" CGO_LDFLAGS="-L$RTX/raytracer-go_amd -Wl,-rpath,$RTX/raytracer-go_amd" go build
 // ($RTX = this repository's root).  main.go then changes only its camera options:
 //   internal.NewCamera(16.0/9.0, 1920, ..., internal.WithGPUs(1), internal.WithSeed(2024))
-// (or RTX_GPUS=1 in the environment, with no change at all), and, to build a World of spheres'
-// BVH on the GPU instead of NewBVHFromWorld's host recursion (bvh.go:138-185; 100k spheres),
+// (or RTX_GPUS=1 in the environment, with no change at all), and, to build the BVH of a World of
+// spheres and quads on the GPU instead of NewBVHFromWorld's host recursion (bvh.go:138-185; 100k spheres),
 // internal.NewBVHFromWorldGPU(world) in place of internal.NewBVHFromWorld(world).
 // Render keeps its CPU path for every scene part, device or option the GPU path does not carry.
 //
@@ -90,8 +90,9 @@ func WithNoiseTolerance(rel float32) CameraOpt {
 	}
 }
 
-// gpuBVH is the tree NewBVHFromWorld would build over a World of spheres, built on the GPU by
-// rtx_scene_create_spheres (NewBVH restated, bvh.go:142-185: the same sort and median split per
+// gpuBVH is the tree NewBVHFromWorld would build over a World of spheres and quads, built on the
+// GPU by rtx_scene_create_spheres, or by rtx_scene_create_world when the World holds a quad
+// (NewBVH restated, bvh.go:142-185: the same sort and median split per
 // node, the axis drawn from the render seed's stream instead of the global rand).  The CPU path
 // (Hit, GetBounds) builds the reference's tree on first use.
 type gpuBVH struct {
@@ -101,8 +102,9 @@ type gpuBVH struct {
 }
 
 // NewBVHFromWorldGPU stands in for NewBVHFromWorld (bvh.go:138-140) when the World holds only
-// spheres: Render on the GPU path builds the tree on the device (10 ms for 100k spheres, where the
-// host recursion takes about 0.5 s), and any CPU use builds the reference's tree.
+// spheres and quads (Box's included): Render on the GPU path builds the tree on the device (10 ms for
+// 100k spheres, where the host recursion takes about 0.5 s), and any CPU use builds the reference's
+// tree.  A World holding anything else (a nested World, a BVH) renders on the CPU path.
 func NewBVHFromWorldGPU(w *World) Hittable { return &gpuBVH{world: w} }
 
 func (g *gpuBVH) cpu() *BVH {
@@ -377,9 +379,9 @@ func (c *Camera) RenderGPU(world Hittable, writer io.Writer, seed uint64, gpus i
 	return err
 }
 
-// sceneOf uploads the world once (rtx_scene_create, or rtx_scene_create_spheres for a
-// NewBVHFromWorldGPU tree): the caller destroys the scene.  Go slices stay pinned only for the
-// call; librtx copies them and keeps no pointer into Go memory.
+// sceneOf uploads the world once (rtx_scene_create, or rtx_scene_create_spheres /
+// rtx_scene_create_world for a NewBVHFromWorldGPU tree): the caller destroys the scene.  Go slices
+// stay pinned only for the call; librtx copies them and keeps no pointer into Go memory.
 func sceneOf(world Hittable, seed uint64) (*C.rtx_scene, error) {
 	scene, _, err := sceneTables(world, seed)
 	return scene, err
@@ -392,22 +394,40 @@ func sceneTables(world Hittable, seed uint64) (*C.rtx_scene, *gpuTables, error) 
 	var scene *C.rtx_scene
 	if g, ok := world.(*gpuBVH); ok {
 		t := &gpuTables{matIdx: map[Material]C.uint32_t{}, texIdx: map[Texture]C.uint32_t{}}
-		for _, h := range g.world.hittables { // spheres in Add order: NewBVH's input list
-			s, ok := h.(*Sphere)
-			if !ok {
+		// the World's list in Add order, NewBVH's input: spheres and quads, each numbered in Add order among its
+		// kind (HitBatch's sphereOf / quadOf are these tables); anything else keeps the CPU path
+		var items []C.int32_t
+		for _, h := range g.world.hittables {
+			switch v := h.(type) {
+			case *Sphere:
+				mi, err := t.material(v.Material)
+				if err != nil {
+					return nil, nil, err
+				}
+				t.spheres = append(t.spheres, C.rtx_sphere{center: vec(v.Center), radius: C.float(v.Radius), material: mi})
+				t.sphereOf = append(t.sphereOf, v)
+				items = append(items, primRef(C.RTX_PRIM_SPHERE, len(t.spheres)-1))
+			case Quad, *Quad: // fields as NewQuad derived them (hittables.go:149-165)
+				q, ok := v.(Quad)
+				if !ok {
+					q = *v.(*Quad)
+				}
+				mi, err := t.material(q.material)
+				if err != nil {
+					return nil, nil, err
+				}
+				t.quads = append(t.quads, C.rtx_quad{
+					q: vec(q.Q), material: mi, u: vec(q.u), d: C.float(q.D), v: vec(q.v), w: vec(q.w), normal: vec(q.normal),
+				})
+				t.quadOf = append(t.quadOf, q)
+				items = append(items, primRef(C.RTX_PRIM_QUAD, len(t.quads)-1))
+			default:
 				return nil, nil, errFallback
 			}
-			mi, err := t.material(s.Material)
-			if err != nil {
-				return nil, nil, err
-			}
-			t.spheres = append(t.spheres, C.rtx_sphere{center: vec(s.Center), radius: C.float(s.Radius), material: mi})
-			t.sphereOf = append(t.sphereOf, s)
 		}
-		if len(t.spheres) == 0 {
+		if len(items) == 0 {
 			return nil, nil, errFallback
 		}
-		pin.Pin(&t.spheres[0])
 		pin.Pin(&t.materials[0])
 		var tex *C.rtx_texture
 		var texels *C.uint32_t
@@ -419,9 +439,25 @@ func sceneTables(world Hittable, seed uint64) (*C.rtx_scene, *gpuTables, error) 
 			pin.Pin(&t.texels[0])
 			texels = &t.texels[0]
 		}
-		if rc := C.rtx_scene_create_spheres(&t.spheres[0], C.uint32_t(len(t.spheres)), &t.materials[0],
-			C.uint32_t(len(t.materials)), tex, C.uint32_t(len(t.textures)), texels, C.uint64_t(len(t.texels)),
-			C.uint64_t(seed), 0, &scene, nil); rc != 0 {
+		if len(t.quads) == 0 { // a World of spheres: the table in order is the list
+			pin.Pin(&t.spheres[0])
+			if rc := C.rtx_scene_create_spheres(&t.spheres[0], C.uint32_t(len(t.spheres)), &t.materials[0],
+				C.uint32_t(len(t.materials)), tex, C.uint32_t(len(t.textures)), texels, C.uint64_t(len(t.texels)),
+				C.uint64_t(seed), 0, &scene, nil); rc != 0 {
+				return nil, nil, rtxErr(rc)
+			}
+			return scene, t, nil
+		}
+		var sph *C.rtx_sphere
+		if len(t.spheres) > 0 {
+			pin.Pin(&t.spheres[0])
+			sph = &t.spheres[0]
+		}
+		pin.Pin(&items[0])
+		pin.Pin(&t.quads[0])
+		if rc := C.rtx_scene_create_world(&items[0], C.uint32_t(len(items)), sph, C.uint32_t(len(t.spheres)),
+			&t.quads[0], C.uint32_t(len(t.quads)), &t.materials[0], C.uint32_t(len(t.materials)), tex,
+			C.uint32_t(len(t.textures)), texels, C.uint64_t(len(t.texels)), C.uint64_t(seed), 0, &scene, nil); rc != 0 {
 			return nil, nil, rtxErr(rc)
 		}
 		return scene, t, nil

@@ -463,6 +463,48 @@ int rtx_scene_create_spheres(const rtx_sphere* spheres, uint32_t n_spheres, cons
                              const uint32_t* texels, uint64_t n_texels, uint64_t bvh_seed, uint64_t bvh_draw0,
                              rtx_scene** out, double* build_ms);
 
+/* The same for a World of spheres and quads (ABI 10, additive): rtx_scene_create for
+ * NewBVHFromWorld(world), the BVH built on the current device.  items[0 .. n_items) is the
+ * World's list in World.Add order, each item RTX_REF_PRIM(RTX_PRIM_SPHERE or RTX_PRIM_QUAD,
+ * index into `spheres` / `quads`).  The scene equals the one rtx_scene_create makes from
+ * NewBVHFromWorld's tree over these tables: the same entries byte for byte, a leaf's index word
+ * being the item's index into the CALLER's table (so rtx_hit.prim and rtx_light.prim name the
+ * caller's primitives).  A quad's box, which the comparators read, is NewQuad's padded one
+ * (hittables.go:161, bvh.go:63-82) computed from q, u, v; its entry takes normal and d from the
+ * record (rtx_quad_init derives them).  The sorts are stable, and the k-th NewBVH call (pre-order)
+ * takes Intn(3) from word bvh_draw0 + k of host stream 1 of bvh_seed, as for spheres
+ * (tests/test_world_bvh_gpu.py against tests/world_bvh_ref.py).
+ *  - items == NULL means every sphere in table order, then every quad in table order; n_items
+ *    must then equal n_spheres + n_quads.
+ *  - A primitive no item names is uploaded, never hit, and is no emitter.  A primitive named
+ *    twice (the same Hittable added twice) gives two entries.  (Where both items of one
+ *    two-item NewBVH call name the same primitive, the node's children are two entries here, as
+ *    the reference tests both; rtx_scene_create reads left == right as the one-element split and
+ *    would emit one.  Hits and colours are the same, the primitive-test count is not.)
+ *  - Returned as RTX_ERR_INVALID_ARG before any device is touched: a NULL out, n_items == 0
+ *    (bvh.go:163 indexes h[0]), n_items > 2^25, an item that is a node ref (>= 0), a list ref, of
+ *    an unknown type or with an index outside its table, and everything rtx_scene_create refuses
+ *    in the primitive, material, texture and texel tables.
+ *  - A box with a NaN bound (a NaN or inf - inf in q, u, v, centre or radius) is out of contract:
+ *    the comparator is no order there.
+ * build_ms (optional) receives the build's wall time.                                  */
+int rtx_scene_create_world(const int32_t* items, uint32_t n_items, const rtx_sphere* spheres, uint32_t n_spheres,
+                           const rtx_quad* quads, uint32_t n_quads, const rtx_material* materials,
+                           uint32_t n_materials, const rtx_texture* textures, uint32_t n_textures,
+                           const uint32_t* texels, uint64_t n_texels, uint64_t bvh_seed, uint64_t bvh_draw0,
+                           rtx_scene** out, double* build_ms);
+
+/* NewQuad (hittables.go:149-165) in float32, every operation rounded on its own: n = Cross(u, v),
+ * normal = n * (1 / float32(sqrt(float64(Dot(n, n))))), d = Dot(normal, q), w = n * (1 / Dot(n, n));
+ * the pads are zero.  A degenerate quad (u x v = 0) gets NaN or infinite fields, as in the
+ * reference.  Host only; a NULL pointer returns RTX_ERR_INVALID_ARG.                   */
+int rtx_quad_init(const float q[3], const float u[3], const float v[3], uint32_t material, rtx_quad* out);
+
+/* Box (hittables.go:200-216): the six quads of the box spanned by the corners a and b, in the
+ * reference's order (front, right, back, left, top, bottom), the negated edges being Scale(dz, -1)
+ * and Scale(dx, -1) as written (their zero components are -0).  Host only.             */
+int rtx_box_quads(const float a[3], const float b[3], uint32_t material, rtx_quad out[6]);
+
 /* Copy the scene's threaded BVH entries (32 B each, rtx_layout.h order) to out when
  * cap is large enough; returns their size in bytes.  For tests and tools.            */
 uint64_t rtx_scene_export(const rtx_scene* scene, void* out, uint64_t cap);

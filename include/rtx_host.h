@@ -58,6 +58,17 @@ uint64_t rtxhost_ppm_encode(const float* rgb, uint32_t width, uint32_t height, c
 int64_t rtxhost_scene_world_spheres(const rtxhost_scene* s, rtx_sphere* out, uint64_t cap, uint64_t* bvh_draw0,
                                     uint64_t* seed);
 
+/* The same for a World of spheres and quads — the inputs of rtx_scene_create_world: the World's
+ * items in World.Add order as RTX_REF_PRIM refs (at most item_cap written), and its sphere and
+ * quad tables, each numbered in Add order among its kind (at most sphere_cap / quad_cap
+ * written; a quad's derived fields as NewQuad made them), material indices into
+ * rtxhost_scene_desc's table; the counts, the global-rand position at NewBVHFromWorld and the
+ * scene seed.  Every output pointer is optional.  Returns the item count, or a negative rtx
+ * error code if the World holds anything but spheres and quads. */
+int64_t rtxhost_scene_world(const rtxhost_scene* s, int32_t* items, uint64_t item_cap, rtx_sphere* spheres,
+                            uint64_t sphere_cap, rtx_quad* quads, uint64_t quad_cap, uint64_t* n_spheres,
+                            uint64_t* n_quads, uint64_t* bvh_draw0, uint64_t* seed);
+
 /* Last error of this thread from an rtxhost_* call. */
 const char* rtxhost_last_error(void);
 

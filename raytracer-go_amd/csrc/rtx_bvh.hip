@@ -1,6 +1,6 @@
 // rtx_bvh.hip — the reference's BVH build on the GPU.
 //
-// NewBVHFromWorld (bvh.go:138-185) over a World of spheres: every NewBVH call draws
+// NewBVHFromWorld (bvh.go:138-185) over a World of spheres and quads: every NewBVH call draws
 // axis = rand.Intn(3) from the global source (before its size switch), then a list of
 // 1 is a leaf (left == right), a list of 2 is ordered by the axis comparator, and a
 // longer list is sorted by it (descending box minimum, HittableCompare{X,Y,Z},
@@ -80,14 +80,34 @@ __device__ __forceinline__ float go_max(float x, float y) {  // math.Max (math.g
     return x > y ? x : y;
 }
 
-// NewSphere's box (hittables.go:85-94): NewAabb(center + (-r), center + r).
-__global__ void prim_boxes(const rtx_sphere* __restrict__ sp, uint32_t n, float* __restrict__ bmin,
-                           float* __restrict__ bmax) {
+// The box of every item of the World's list (HittableCompare* reads GetBounds(), bvh.go:187-218), one thread per
+// item.  A sphere: NewSphere's box (hittables.go:85-94), NewAabb(center + (-r), center + r).  A quad: NewQuad's
+// (hittables.go:161), NewAabb(Q, (Q + u) + v).GetPaddedAabb() (bvh.go:28-34, 63-82): an axis thinner than 0.0001 grows
+// by that much on both sides (the comparison is false for a NaN difference).  Every operation is rounded on its own
+// (the unit is built without contraction).  The refs were checked on the host: a sphere or a quad of its table.
+__global__ void item_boxes(const int32_t* __restrict__ items, uint32_t n, const rtx_sphere* __restrict__ sp,
+                           const rtx_quad* __restrict__ qd, float* __restrict__ bmin, float* __restrict__ bmax) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float r = sp[i].radius, nr = r * -1.0f;
+    const uint32_t p = ~(uint32_t)items[i], index = p & 0x0FFFFFFFu;
+    if ((p >> 28) == RTX_PRIM_QUAD) {
+        const rtx_quad& q = qd[index];
+        const float eps = 0.0001f;
+        for (int a = 0; a < 3; ++a) {
+            const float p1 = q.q[a], p2 = (q.q[a] + q.u[a]) + q.v[a];
+            float lo = go_min(p1, p2), hi = go_max(p1, p2);
+            if (hi - lo < eps) {
+                lo = lo - eps;
+                hi = hi + eps;
+            }
+            bmin[3 * i + a] = lo;
+            bmax[3 * i + a] = hi;
+        }
+        return;
+    }
+    const float r = sp[index].radius, nr = r * -1.0f;
     for (int a = 0; a < 3; ++a) {
-        const float p1 = sp[i].center[a] + nr, p2 = sp[i].center[a] + r;
+        const float p1 = sp[index].center[a] + nr, p2 = sp[index].center[a] + r;
         bmin[3 * i + a] = go_min(p1, p2);
         bmax[3 * i + a] = go_max(p1, p2);
     }
@@ -148,9 +168,24 @@ __global__ void node_boxes(const DevNode* __restrict__ nodes, const uint32_t* __
     }
 }
 
-// A sphere's entry; `index` is its place in the caller's table (World.Add order), as rtx_scene_create's emit()
-// writes it: rtx_hit.prim and rtx_light.prim are read from that word.
-__device__ __forceinline__ void put_prim(rtx_entry* e, const rtx_sphere& s, uint32_t index) {
+// A leaf item's entry, as rtx_scene_create's emit() writes it for the same ref.  The index word is the index into
+// the CALLER's table (the ref's own), not the list position: rtx_hit.prim and rtx_light.prim are read from that word.
+__device__ __forceinline__ void put_prim(rtx_entry* e, int32_t ref, const rtx_sphere* __restrict__ sp,
+                                         const rtx_quad* __restrict__ qd) {
+    const uint32_t p = ~(uint32_t)ref, index = p & 0x0FFFFFFFu;
+    if ((p >> 28) == RTX_PRIM_QUAD) {  // (normal, D | quad, 0, 0, tag)
+        const rtx_quad& q = qd[index];
+        e->a[0] = q.normal[0];
+        e->a[1] = q.normal[1];
+        e->a[2] = q.normal[2];
+        e->a[3] = q.d;
+        e->b[0] = __int_as_float((int)index);
+        e->b[1] = 0.0f;
+        e->b[2] = 0.0f;
+        e->b[3] = __int_as_float(RTX_E_QUAD);
+        return;
+    }
+    const rtx_sphere& s = sp[index];
     e->a[0] = s.center[0];
     e->a[1] = s.center[1];
     e->a[2] = s.center[2];
@@ -164,7 +199,8 @@ __device__ __forceinline__ void put_prim(rtx_entry* e, const rtx_sphere& s, uint
 // The threaded pre-order entries (rtx_layout.h), as rtx_scene_create's emit() writes
 // them for the same tree: a leaf of one prim is emitted once (left == right).
 __global__ void emit_entries(const DevNode* __restrict__ nodes, uint32_t n_nodes, const uint32_t* __restrict__ perm,
-                             const rtx_sphere* __restrict__ sp, const float* __restrict__ nmin,
+                             const int32_t* __restrict__ items, const rtx_sphere* __restrict__ sp,
+                             const rtx_quad* __restrict__ qd, const float* __restrict__ nmin,
                              const float* __restrict__ nmax, rtx_entry* __restrict__ out) {
     const uint32_t id = blockIdx.x * 256 + threadIdx.x;
     if (id >= n_nodes) return;
@@ -182,8 +218,7 @@ __global__ void emit_entries(const DevNode* __restrict__ nodes, uint32_t n_nodes
     if (nd.n <= 2) {
         for (uint32_t k = 0; k < nd.n; ++k) {
             rtx_entry p;
-            const uint32_t index = perm[nd.off + k];
-            put_prim(&p, sp[index], index);
+            put_prim(&p, items[perm[nd.off + k]], sp, qd);
             out[nd.entry + 1 + k] = p;
         }
     }
@@ -197,8 +232,9 @@ __global__ void emit_entries(const DevNode* __restrict__ nodes, uint32_t n_nodes
         if (e_ != hipSuccess) return fail(e_); \
     } while (0)
 
-hipError_t build_sphere_bvh(const rtx_sphere* spheres, uint32_t n, uint64_t seed, uint64_t draw0,
-                            std::vector<rtx_entry>& out, double* build_ms) {
+hipError_t build_world_bvh(const int32_t* items, uint32_t n, const rtx_sphere* spheres, uint32_t n_spheres,
+                           const rtx_quad* quads, uint32_t n_quads, uint64_t seed, uint64_t draw0,
+                           std::vector<rtx_entry>& out, double* build_ms) {
     const auto t0 = std::chrono::steady_clock::now();
     // ---- the recursion's shape (sizes only): nodes in pre-order ------------------------
     std::map<uint32_t, uint64_t> calls_memo, entries_memo;
@@ -245,6 +281,8 @@ hipError_t build_sphere_bvh(const rtx_sphere* spheres, uint32_t n, uint64_t seed
     const uint64_t n_entries = entries(n);
     // ---- device buffers ----------------------------------------------------------------
     rtx_sphere* d_sp = nullptr;
+    rtx_quad* d_qd = nullptr;
+    int32_t* d_items = nullptr;
     float *d_pmin = nullptr, *d_pmax = nullptr, *d_nmin = nullptr, *d_nmax = nullptr;
     uint32_t *d_perm = nullptr, *d_perm2 = nullptr, *d_off = nullptr, *d_ids = nullptr;
     uint8_t* d_axis = nullptr;
@@ -253,8 +291,8 @@ hipError_t build_sphere_bvh(const rtx_sphere* spheres, uint32_t n, uint64_t seed
     rtx_entry* d_out = nullptr;
     void* d_tmp = nullptr;
     auto release = [&]() {
-        for (void* p : {(void*)d_sp, (void*)d_pmin, (void*)d_pmax, (void*)d_nmin, (void*)d_nmax, (void*)d_perm,
-                        (void*)d_perm2, (void*)d_off, (void*)d_ids, (void*)d_axis, (void*)d_keys, (void*)d_keys2,
+        for (void* p : {(void*)d_sp, (void*)d_qd, (void*)d_items, (void*)d_pmin, (void*)d_pmax, (void*)d_nmin,
+                        (void*)d_nmax, (void*)d_perm, (void*)d_perm2, (void*)d_off, (void*)d_ids, (void*)d_axis, (void*)d_keys, (void*)d_keys2,
                         (void*)d_nodes, (void*)d_out, d_tmp})
             if (p) (void)hipFree(p);
     };
@@ -263,7 +301,10 @@ hipError_t build_sphere_bvh(const rtx_sphere* spheres, uint32_t n, uint64_t seed
         return e;
     };
     const size_t N = n, M = nodes.size();
-    BVH_TRY(hipMalloc(&d_sp, N * sizeof(rtx_sphere)));
+    // (an empty table is never read: no checked ref names it)
+    if (n_spheres) BVH_TRY(hipMalloc(&d_sp, (size_t)n_spheres * sizeof(rtx_sphere)));
+    if (n_quads) BVH_TRY(hipMalloc(&d_qd, (size_t)n_quads * sizeof(rtx_quad)));
+    BVH_TRY(hipMalloc(&d_items, N * 4));
     BVH_TRY(hipMalloc(&d_pmin, N * 12));
     BVH_TRY(hipMalloc(&d_pmax, N * 12));
     BVH_TRY(hipMalloc(&d_nmin, M * 12));
@@ -280,12 +321,14 @@ hipError_t build_sphere_bvh(const rtx_sphere* spheres, uint32_t n, uint64_t seed
     size_t tmp_bytes = 0;
     BVH_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_keys, d_keys2, d_perm, d_perm2, (int)N));
     BVH_TRY(hipMalloc(&d_tmp, tmp_bytes));
-    BVH_TRY(hipMemcpy(d_sp, spheres, N * sizeof(rtx_sphere), hipMemcpyHostToDevice));
+    if (n_spheres) BVH_TRY(hipMemcpy(d_sp, spheres, (size_t)n_spheres * sizeof(rtx_sphere), hipMemcpyHostToDevice));
+    if (n_quads) BVH_TRY(hipMemcpy(d_qd, quads, (size_t)n_quads * sizeof(rtx_quad), hipMemcpyHostToDevice));
+    BVH_TRY(hipMemcpy(d_items, items, N * 4, hipMemcpyHostToDevice));
     std::vector<uint32_t> iota(N);
     for (uint32_t i = 0; i < n; ++i) iota[i] = i;  // the World's order (:144-145 copies it)
     BVH_TRY(hipMemcpy(d_perm, iota.data(), N * 4, hipMemcpyHostToDevice));
     const uint32_t grid_n = (uint32_t)((N + 255) / 256);
-    hipLaunchKernelGGL(prim_boxes, dim3(grid_n), dim3(256), 0, 0, d_sp, n, d_pmin, d_pmax);
+    hipLaunchKernelGGL(item_boxes, dim3(grid_n), dim3(256), 0, 0, d_items, n, d_sp, d_qd, d_pmin, d_pmax);
     BVH_TRY(hipGetLastError());
     // ---- one stable sort per recursion depth -------------------------------------------
     std::vector<std::vector<uint32_t>> by_depth(max_depth + 1);
@@ -338,7 +381,7 @@ hipError_t build_sphere_bvh(const rtx_sphere* spheres, uint32_t n, uint64_t seed
         BVH_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(emit_entries, dim3((uint32_t)((M + 255) / 256)), dim3(256), 0, 0, d_nodes, (uint32_t)M, d_perm,
-                       d_sp, d_nmin, d_nmax, d_out);
+                       d_items, d_sp, d_qd, d_nmin, d_nmax, d_out);
     BVH_TRY(hipGetLastError());
     out.resize(n_entries);
     BVH_TRY(hipMemcpy(out.data(), d_out, n_entries * sizeof(rtx_entry), hipMemcpyDeviceToHost));
@@ -346,6 +389,13 @@ hipError_t build_sphere_bvh(const rtx_sphere* spheres, uint32_t n, uint64_t seed
     if (build_ms)
         *build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return hipSuccess;
+}
+
+hipError_t build_sphere_bvh(const rtx_sphere* spheres, uint32_t n, uint64_t seed, uint64_t draw0,
+                            std::vector<rtx_entry>& out, double* build_ms) {
+    std::vector<int32_t> items(n);
+    for (uint32_t i = 0; i < n; ++i) items[i] = RTX_REF_PRIM(RTX_PRIM_SPHERE, i);
+    return build_world_bvh(items.data(), n, spheres, n, nullptr, 0, seed, draw0, out, build_ms);
 }
 
 }  // namespace rtxd

@@ -120,6 +120,54 @@ int rtx_scene_create_spheres(const rtx_sphere* spheres, uint32_t n_spheres, cons
     return finish_scene(s, &d, out);
 }
 
+int rtx_scene_create_world(const int32_t* items, uint32_t n_items, const rtx_sphere* spheres, uint32_t n_spheres,
+                           const rtx_quad* quads, uint32_t n_quads, const rtx_material* materials, uint32_t n_materials,
+                           const rtx_texture* textures, uint32_t n_textures, const uint32_t* texels, uint64_t n_texels,
+                           uint64_t bvh_seed, uint64_t bvh_draw0, rtx_scene** out, double* build_ms) {
+    g_last_error.clear();
+    if (!out) return fail(RTX_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (n_items == 0) return fail(RTX_ERR_INVALID_ARG, "empty World (NewBVH indexes h[0], bvh.go:163)");
+    if (n_items > (1u << 25)) return fail(RTX_ERR_INVALID_ARG, "too many items for the GPU BVH build");
+    if (!items && (uint64_t)n_spheres + n_quads != n_items)
+        return fail(RTX_ERR_INVALID_ARG, "items is NULL: n_items %u is not n_spheres + n_quads (%u + %u)", n_items,
+                    n_spheres, n_quads);
+    rtx_scene_desc d{};
+    d.spheres = spheres;
+    d.n_spheres = n_spheres;
+    d.quads = quads;
+    d.n_quads = n_quads;
+    d.materials = materials;
+    d.n_materials = n_materials;
+    d.textures = textures;
+    d.n_textures = n_textures;
+    d.texels = texels;
+    d.n_texels = n_texels;
+    if (int rc = validate_tables(&d)) return rc;
+    std::vector<int32_t> every;
+    if (!items) {  // every sphere in table order, then every quad
+        every.reserve(n_items);
+        for (uint32_t i = 0; i < n_spheres; ++i) every.push_back(RTX_REF_PRIM(RTX_PRIM_SPHERE, i));
+        for (uint32_t i = 0; i < n_quads; ++i) every.push_back(RTX_REF_PRIM(RTX_PRIM_QUAD, i));
+        items = every.data();
+    }
+    if (int rc = check_world_items(&d, items, n_items)) return rc;
+    int cur = 0;
+    if (hipGetDevice(&cur) != hipSuccess) return fail(RTX_ERR_NO_DEVICE, "no HIP device");
+    rtx_scene* s = new rtx_scene();
+    double ms = 0;
+    hipError_t e = rtxd::build_world_bvh(items, n_items, spheres, n_spheres, quads, n_quads, bvh_seed, bvh_draw0,
+                                         s->base, &ms);
+    if (e != hipSuccess) {
+        delete s;
+        return hip_fail(e, "GPU BVH build");
+    }
+    if (build_ms) *build_ms = ms;
+    rank_spheres(s);
+    adopt_topology(s, 0u, &d);
+    return finish_scene(s, &d, out);
+}
+
 void rtx_scene_destroy(rtx_scene* s) {
     if (!s) return;
     for (auto& kv : s->copies) drop_copy(*kv.second);

@@ -80,6 +80,8 @@ uint32_t env_knob(const char* name, long dflt, long lo, long hi);
 int check_acyclic(const rtx_scene_desc* d);
 int emit(const rtx_scene_desc* d, int32_t root, std::vector<rtx_entry>& out);
 int validate_tables(const rtx_scene_desc* d);
+// The items of a World handed to the GPU BVH build: each a sphere or a quad of d's tables.
+int check_world_items(const rtx_scene_desc* d, const int32_t* items, uint32_t n_items);
 void quad_table(const rtx_scene_desc* d, std::vector<float>& tab);
 void rank_spheres(rtx_scene* s);
 void adopt_topology(rtx_scene* s, uint32_t flags, const rtx_scene_desc* d);

@@ -214,6 +214,24 @@ int validate_tables(const rtx_scene_desc* d) {
     return RTX_OK;
 }
 
+// The list of a World for rtx_scene_create_world: NewBVH's input holds spheres and quads only (a node, a nested
+// World, an unknown type or an index outside its table is refused; a primitive may be named twice or not at all).
+int check_world_items(const rtx_scene_desc* d, const int32_t* items, uint32_t n_items) {
+    for (uint32_t i = 0; i < n_items; ++i) {
+        const int32_t ref = items[i];
+        if (ref >= 0) return fail(RTX_ERR_INVALID_ARG, "item %u: a node ref (%d) is no item of a World", i, ref);
+        const uint32_t type = ((uint32_t)(~ref)) >> 28;
+        if (type == RTX_PRIM_LIST) return fail(RTX_ERR_INVALID_ARG, "item %u: a nested World is not built on the GPU", i);
+        if (type != RTX_PRIM_SPHERE && type != RTX_PRIM_QUAD)
+            return fail(RTX_ERR_INVALID_ARG, "item %u: unknown primitive type %u", i, type);
+        if (check_ref(d, ref)) {
+            const std::string why = g_last_error;
+            return fail(RTX_ERR_INVALID_ARG, "item %u: %s", i, why.c_str());
+        }
+    }
+    return RTX_OK;
+}
+
 // The quad table of a scene description (rtx_layout.h): (Q, material), (u, 0), (v, 0), (w, 0).
 void quad_table(const rtx_scene_desc* d, std::vector<float>& tab) {
     tab.assign((size_t)d->n_quads * 16, 0.0f);
@@ -851,6 +869,67 @@ uint64_t rtx_scene_device_bytes(const rtx_scene* s) {
     return s->base.size() * sizeof(rtx_entry) + s->quadtab.size() * sizeof(float) +
            s->materials.size() * sizeof(rtx_material) +
            s->textures.size() * sizeof(rtx_texture) + s->texels.size() * sizeof(uint32_t);
+}
+
+// MinF32 / MaxF32 (math.go:38-44): math.Min / math.Max of float32 values.
+static float min_f32(float x, float y) {
+    if ((std::isinf(x) && x < 0) || (std::isinf(y) && y < 0)) return -std::numeric_limits<float>::infinity();
+    if (std::isnan(x) || std::isnan(y)) return std::numeric_limits<float>::quiet_NaN();
+    if (x == 0 && x == y) return std::signbit(x) ? x : y;
+    return x < y ? x : y;
+}
+static float max_f32(float x, float y) {
+    if ((std::isinf(x) && x > 0) || (std::isinf(y) && y > 0)) return std::numeric_limits<float>::infinity();
+    if (std::isnan(x) || std::isnan(y)) return std::numeric_limits<float>::quiet_NaN();
+    if (x == 0 && x == y) return std::signbit(x) ? y : x;
+    return x > y ? x : y;
+}
+
+// NewQuad (hittables.go:149-165) in float32, every operation rounded on its own (the unit is built without
+// contraction): Cross vec3.go:129-135, Dot :137-139 (summed left to right), Unit :103-107 (the length through float64).
+int rtx_quad_init(const float q[3], const float u[3], const float v[3], uint32_t material, rtx_quad* out) {
+    g_last_error.clear();
+    if (!q || !u || !v || !out) return fail(RTX_ERR_INVALID_ARG, "NULL argument");
+    const float n[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
+    const float nn = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+    const float inv_len = 1.0f / (float)std::sqrt((double)nn);
+    const float inv = 1.0f / nn;
+    rtx_quad r;
+    std::memset(&r, 0, sizeof(r));
+    for (int k = 0; k < 3; ++k) {
+        r.q[k] = q[k];
+        r.u[k] = u[k];
+        r.v[k] = v[k];
+        r.normal[k] = n[k] * inv_len;
+        r.w[k] = n[k] * inv;
+    }
+    r.d = r.normal[0] * q[0] + r.normal[1] * q[1] + r.normal[2] * q[2];
+    r.material = material;
+    *out = r;
+    return RTX_OK;
+}
+
+// Box (hittables.go:200-216): the six sides in its order, Scale(dz, -1) and Scale(dx, -1) as written (their zero
+// components become -0).
+int rtx_box_quads(const float a[3], const float b[3], uint32_t material, rtx_quad out[6]) {
+    g_last_error.clear();
+    if (!a || !b || !out) return fail(RTX_ERR_INVALID_ARG, "NULL argument");
+    float mn[3], mx[3];
+    for (int k = 0; k < 3; ++k) {
+        mn[k] = min_f32(a[k], b[k]);
+        mx[k] = max_f32(a[k], b[k]);
+    }
+    const float dx[3] = {mx[0] - mn[0], 0.0f, 0.0f}, dy[3] = {0.0f, mx[1] - mn[1], 0.0f}, dz[3] = {0.0f, 0.0f, mx[2] - mn[2]};
+    const float ndx[3] = {dx[0] * -1.0f, dx[1] * -1.0f, dx[2] * -1.0f}, ndz[3] = {dz[0] * -1.0f, dz[1] * -1.0f, dz[2] * -1.0f};
+    const float q0[3] = {mn[0], mn[1], mx[2]}, q1[3] = {mx[0], mn[1], mx[2]}, q2[3] = {mx[0], mn[1], mn[2]},
+                q3[3] = {mn[0], mn[1], mn[2]}, q4[3] = {mn[0], mx[1], mx[2]};
+    rtx_quad_init(q0, dx, dy, material, &out[0]);
+    rtx_quad_init(q1, ndz, dy, material, &out[1]);
+    rtx_quad_init(q2, ndx, dy, material, &out[2]);
+    rtx_quad_init(q3, dz, dy, material, &out[3]);
+    rtx_quad_init(q4, dx, ndz, material, &out[4]);
+    rtx_quad_init(q3, dx, dz, material, &out[5]);
+    return RTX_OK;
 }
 
 }  // extern "C"

@@ -66,6 +66,60 @@ int64_t rtxhost_scene_world_spheres(const rtxhost_scene* s, rtx_sphere* out, uin
     return (int64_t)hs.size();
 }
 
+int64_t rtxhost_scene_world(const rtxhost_scene* s, int32_t* items, uint64_t item_cap, rtx_sphere* spheres,
+                            uint64_t sphere_cap, rtx_quad* quads, uint64_t quad_cap, uint64_t* n_spheres,
+                            uint64_t* n_quads, uint64_t* bvh_draw0, uint64_t* seed) {
+    g_err.clear();
+    if (!s || !s->spec.list) return set_err(Error{RTX_ERR_INVALID_ARG, "scene has no World list"});
+    const auto& hs = s->spec.list->hittables;
+    uint64_t ns = 0, nq = 0;
+    for (size_t i = 0; i < hs.size(); ++i) {
+        const Material* mat = nullptr;
+        int32_t ref = 0;
+        if (auto sp = dynamic_cast<const Sphere*>(hs[i].get())) {
+            mat = sp->Mat.get();
+            ref = RTX_REF_PRIM(RTX_PRIM_SPHERE, ns);
+        } else if (auto q = dynamic_cast<const Quad*>(hs[i].get())) {
+            mat = q->material.get();
+            ref = RTX_REF_PRIM(RTX_PRIM_QUAD, nq);
+        } else {
+            return set_err(Error{RTX_ERR_UNSUPPORTED, "the World holds an item that is neither a sphere nor a quad"});
+        }
+        auto it = s->flat.mat_index.find(mat);
+        if (it == s->flat.mat_index.end()) return set_err(Error{RTX_ERR_INVALID_ARG, "material not flattened"});
+        if (items && i < item_cap) items[i] = ref;
+        if (auto sp = dynamic_cast<const Sphere*>(hs[i].get())) {
+            if (spheres && ns < sphere_cap) {
+                rtx_sphere r{};
+                r.center[0] = sp->Center.X; r.center[1] = sp->Center.Y; r.center[2] = sp->Center.Z;
+                r.radius = sp->Radius;
+                r.material = it->second;
+                spheres[ns] = r;
+            }
+            ++ns;
+        } else {
+            auto q = static_cast<const Quad*>(hs[i].get());
+            if (quads && nq < quad_cap) {  // the fields as NewQuad derived them (flatten.cpp writes the same record)
+                rtx_quad r{};
+                r.q[0] = q->Q.X; r.q[1] = q->Q.Y; r.q[2] = q->Q.Z;
+                r.u[0] = q->u.X; r.u[1] = q->u.Y; r.u[2] = q->u.Z;
+                r.v[0] = q->v.X; r.v[1] = q->v.Y; r.v[2] = q->v.Z;
+                r.w[0] = q->w.X; r.w[1] = q->w.Y; r.w[2] = q->w.Z;
+                r.normal[0] = q->normal.X; r.normal[1] = q->normal.Y; r.normal[2] = q->normal.Z;
+                r.d = q->D;
+                r.material = it->second;
+                quads[nq] = r;
+            }
+            ++nq;
+        }
+    }
+    if (n_spheres) *n_spheres = ns;
+    if (n_quads) *n_quads = nq;
+    if (bvh_draw0) *bvh_draw0 = s->spec.bvh_draw0;
+    if (seed) *seed = s->spec.seed;
+    return (int64_t)hs.size();
+}
+
 const rtx_scene_desc* rtxhost_scene_desc(const rtxhost_scene* s) { return s ? &s->flat.desc : nullptr; }
 
 int rtxhost_synthetic_earth_ycbcr(uint64_t seed, int32_t w, int32_t h, uint8_t* y, uint8_t* cb, uint8_t* cr) {

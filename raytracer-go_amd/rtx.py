@@ -291,11 +291,13 @@ RTX_SYMBOLS = [
     "rtx_lights", "rtx_scene_lights", "rtx_direct_device", "rtx_direct", "rtx_accum_add_direct",
     # multiple importance sampling of the direct light (ABI 10, additive)
     "rtx_prim_lights", "rtx_emitter_weight_device", "rtx_emitter_weight", "rtx_accum_add_mis",
+    # GPU BVH build for a World of spheres and quads, and the quad constructors (ABI 10, additive)
+    "rtx_scene_create_world", "rtx_quad_init", "rtx_box_quads",
 ]
 RTXHOST_SYMBOLS = [
     "rtxhost_build_scene", "rtxhost_scene_free", "rtxhost_scene_desc", "rtxhost_scene_camera",
     "rtxhost_render_ppm", "rtxhost_ppm_encode", "rtxhost_last_error", "rtxhost_scene_world_spheres",
-    "rtxhost_synthetic_earth_ycbcr", "rtxhost_ycbcr_rgba",
+    "rtxhost_synthetic_earth_ycbcr", "rtxhost_ycbcr_rgba", "rtxhost_scene_world",
 ]
 
 _lib = None
@@ -377,6 +379,16 @@ def load() -> ctypes.CDLL:
                                            c_uint32, POINTER(c_uint32), c_uint64, c_uint64, c_uint64,
                                            POINTER(c_void_p), POINTER(c_double)]
     L.rtx_scene_create_spheres.restype = c_int
+    if hasattr(L, "rtx_scene_create_world"):  # ABI 10, additive (RTX_LIB may name an older build for A/B)
+        L.rtx_scene_create_world.argtypes = [POINTER(c_int32), c_uint32, POINTER(Sphere), c_uint32, POINTER(Quad),
+                                             c_uint32, POINTER(Material), c_uint32, POINTER(Texture), c_uint32,
+                                             POINTER(c_uint32), c_uint64, c_uint64, c_uint64, POINTER(c_void_p),
+                                             POINTER(c_double)]
+        L.rtx_scene_create_world.restype = c_int
+        L.rtx_quad_init.argtypes = [POINTER(c_float), POINTER(c_float), POINTER(c_float), c_uint32, POINTER(Quad)]
+        L.rtx_quad_init.restype = c_int
+        L.rtx_box_quads.argtypes = [POINTER(c_float), POINTER(c_float), c_uint32, POINTER(Quad)]
+        L.rtx_box_quads.restype = c_int
     L.rtx_scene_export.argtypes = [c_void_p, c_void_p, c_uint64]
     L.rtx_scene_export.restype = c_uint64
     L.rtx_release_device_memory.argtypes = [c_int]
@@ -503,12 +515,32 @@ def load_host() -> ctypes.CDLL:
     H.rtxhost_last_error.restype = c_char_p
     H.rtxhost_scene_world_spheres.argtypes = [c_void_p, POINTER(Sphere), c_uint64, POINTER(c_uint64), POINTER(c_uint64)]
     H.rtxhost_scene_world_spheres.restype = ctypes.c_int64
+    H.rtxhost_scene_world.argtypes = [c_void_p, POINTER(c_int32), c_uint64, POINTER(Sphere), c_uint64, POINTER(Quad),
+                                      c_uint64, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64),
+                                      POINTER(c_uint64)]
+    H.rtxhost_scene_world.restype = ctypes.c_int64
     H.rtxhost_synthetic_earth_ycbcr.argtypes = [c_uint64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
     H.rtxhost_synthetic_earth_ycbcr.restype = c_int
     H.rtxhost_ycbcr_rgba.argtypes = [ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint8, POINTER(c_uint32)]
     H.rtxhost_ycbcr_rgba.restype = None
     _host = H
     return H
+
+
+def quad(Q, u, v, material: int) -> "Quad":
+    """rtx_quad_init: NewQuad (hittables.go:149-165), the derived fields w, normal and d filled in."""
+    out = Quad()
+    vec = [(c_float * 3)(*[float(x) for x in a]) for a in (Q, u, v)]
+    check(load().rtx_quad_init(vec[0], vec[1], vec[2], material, ctypes.byref(out)), "rtx_quad_init")
+    return out
+
+
+def box(a, b, material: int):
+    """rtx_box_quads: the six quads of Box(a, b) (hittables.go:200-216), a ctypes array of Quad."""
+    out = (Quad * 6)()
+    vec = [(c_float * 3)(*[float(x) for x in p]) for p in (a, b)]
+    check(load().rtx_box_quads(vec[0], vec[1], material, out), "rtx_box_quads")
+    return out
 
 
 class RtxError(RuntimeError):
@@ -560,6 +592,20 @@ class HostScene:
         H.rtxhost_scene_world_spheres(self._h, arr, n, ctypes.byref(draw0), ctypes.byref(seed))
         return arr, int(n), draw0.value, seed.value
 
+    def world(self):
+        """(items, spheres, quads, BVH draw position, seed): rtx_scene_create_world's inputs.  items: int32 refs in
+        World.Add order (a ctypes array); spheres, quads: ctypes arrays numbered in Add order per kind (their lengths
+        are the counts), materials indexing self.desc's table."""
+        H = load_host()
+        ns, nq, draw0, seed = c_uint64(), c_uint64(), c_uint64(), c_uint64()
+        n = H.rtxhost_scene_world(self._h, None, 0, None, 0, None, 0, ctypes.byref(ns), ctypes.byref(nq), None, None)
+        if n < 0:
+            raise RtxError(int(n), H.rtxhost_last_error().decode())
+        items, spheres, quads = (c_int32 * int(n))(), (Sphere * ns.value)(), (Quad * nq.value)()
+        H.rtxhost_scene_world(self._h, items, n, spheres, ns.value, quads, nq.value, None, None, ctypes.byref(draw0),
+                              ctypes.byref(seed))
+        return items, spheres, quads, draw0.value, seed.value
+
     def close(self) -> None:
         if self._h:
             load_host().rtxhost_scene_free(self._h)
@@ -602,6 +648,35 @@ class DeviceScene:
         obj = cls(handle=h)
         obj.build_ms = ms.value
         return obj
+
+    @classmethod
+    def from_tables(cls, items, spheres, quads, tables, seed: int, draw0: int = 0) -> "DeviceScene":
+        """rtx_scene_create_world: NewBVHFromWorld of a World of spheres and quads, built on the GPU.  items: the
+        World's list in Add order, rtx.ref_prim refs (a ctypes int32 array or a sequence), or None for every sphere,
+        then every quad; spheres, quads: ctypes arrays (or None); tables: a SceneDesc (or a pointer to one) whose
+        material, texture and texel tables the scene takes.  Sets build_ms."""
+        L = load()
+        t = tables.contents if hasattr(tables, "contents") else tables
+        ns, nq = (len(spheres) if spheres is not None else 0), (len(quads) if quads is not None else 0)
+        if items is None:
+            n_items = ns + nq
+        else:
+            if not isinstance(items, ctypes.Array):
+                items = (c_int32 * len(items))(*[int(r) for r in items])
+            n_items = len(items)
+        h, ms = c_void_p(), c_double()
+        check(L.rtx_scene_create_world(items, n_items, spheres if ns else None, ns, quads if nq else None, nq,
+                                       t.materials, t.n_materials, t.textures, t.n_textures, t.texels, t.n_texels,
+                                       seed, draw0, ctypes.byref(h), ctypes.byref(ms)), "rtx_scene_create_world")
+        obj = cls(handle=h)
+        obj.build_ms = ms.value
+        return obj
+
+    @classmethod
+    def from_world(cls, host: "HostScene") -> "DeviceScene":
+        """rtx_scene_create_world over host's World (spheres and quads): its BVH built on the GPU."""
+        items, spheres, quads, draw0, seed = host.world()
+        return cls.from_tables(items, spheres, quads, host.desc, seed, draw0)
 
     def export(self) -> bytes:
         L = load()
