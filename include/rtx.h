@@ -568,7 +568,8 @@ int rtx_render_ppm_ex(rtx_scene* scene, const rtx_camera* cam, uint64_t seed, in
 typedef struct rtx_accum rtx_accum;
 
 /* Validates as rtx_render_region_device does; allocates and zeroes 24 B per pixel slot of the
- * region's shard (64-pixel tiles, ragged tiles padded) on the current device. */
+ * region's shard (64-pixel tiles, ragged tiles padded) on the current device.  The zeroes are in place on return: a
+ * pass may follow at once on any stream, a non-blocking one included. */
 int rtx_accum_create(rtx_scene* scene, const rtx_camera* cam, uint64_t seed, const rtx_region* region,
                      rtx_accum** out);
 
@@ -610,7 +611,8 @@ int rtx_accum_resolve(rtx_accum* accum, float* out_rgb, float* out_var, float re
  * rtx_render_ppm's at samples_per_pixel = n.  Blocking. */
 int rtx_accum_ppm(rtx_accum* accum, char* out_text, uint64_t capacity, uint64_t* out_len);
 
-/* Back to n = 0 with S and Q zero, after everything enqueued on the device.  Blocking. */
+/* Back to n = 0 with S and Q zero, after everything enqueued on the device.  Blocking: S and Q are zero on return,
+ * so a pass may follow at once on any stream. */
 int rtx_accum_reset(rtx_accum* accum);
 
 /* Frees the accumulator's device memory (NULL is a no-op).  Blocking. */

@@ -124,10 +124,10 @@ int rtx_accum_create(rtx_scene* s, const rtx_camera* cam, uint64_t seed, const r
     a->tile_w_log2 = make_params(s, c, layout_slot(s, cam), cam, seed, region, nullptr).tile_w_log2;
     a->slots = (uint64_t)rtxd::tiles_x_of(region->width, a->tile_w_log2) * rtxd::tiles_y_of(a->rows, a->tile_w_log2) * 64;
     hipError_t e = a->sums.reserve(std::max<size_t>(2 * accum_bytes(a), sizeof(float)));
-    if (e == hipSuccess) e = hipMemset(a->sums.ptr, 0, a->sums.bytes);
+    if (e == hipSuccess) e = zero_now(a->sums.ptr, a->sums.bytes);  // (the first pass may run on any stream, at once)
     if (e == hipSuccess) e = a->noisy.reserve(sizeof(unsigned long long));
     if (e == hipSuccess) e = a->adapt.reserve(a->adapt_bytes());
-    if (e == hipSuccess) e = hipMemset(a->adapt.ptr, 0, a->adapt.bytes);  // every tile open
+    if (e == hipSuccess) e = zero_now(a->adapt.ptr, a->adapt.bytes);  // every tile open
     if (e != hipSuccess) {
         a->sums.release();
         a->noisy.release();
@@ -417,8 +417,8 @@ int rtx_accum_reset(rtx_accum* a) {
     if (int rc = accum_device(a)) return rc;
     std::lock_guard<std::mutex> lk(a->scene->mu);
     HIP_TRY(hipDeviceSynchronize());  // passes and resolves in flight, on any stream
-    HIP_TRY(hipMemset(a->sums.ptr, 0, a->sums.bytes));
-    HIP_TRY(hipMemset(a->adapt.ptr, 0, a->adapt.bytes));  // every tile open again
+    HIP_TRY(zero_now(a->sums.ptr, a->sums.bytes));
+    HIP_TRY(zero_now(a->adapt.ptr, a->adapt.bytes));  // every tile open again
     a->adaptive = false;
     a->direct = false;
     a->mis = false;

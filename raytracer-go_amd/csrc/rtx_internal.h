@@ -215,6 +215,11 @@ extern std::mutex g_ppm_mu;
 extern std::map<int, DeviceBuffer> g_ppm;
 
 hipError_t copy_to_host(void* dst, const void* src, size_t bytes, hipStream_t st);
+// Zero device memory and return when it IS zero.  The host hipMemset only enqueues the fill on the null stream
+// (measured: it returns in 5 us with the fill of 1 GiB, or the null stream's earlier work, still running), and a
+// non-blocking stream does not wait for the null stream: work enqueued on one right after would meet the old
+// contents, or have its own results wiped later.
+hipError_t zero_now(void* ptr, size_t bytes);
 
 uint32_t* kerr_word(int device);
 int kerr_take(int device);

@@ -57,6 +57,11 @@ hipError_t copy_to_host(void* dst, const void* src, size_t bytes, hipStream_t st
     return e;
 }
 
+hipError_t zero_now(void* ptr, size_t bytes) {
+    const hipError_t e = hipMemsetAsync(ptr, 0, bytes, nullptr);
+    return e == hipSuccess ? hipStreamSynchronize(nullptr) : e;
+}
+
 namespace {
 void release_stage_locked() {
     for (int i = 0; i < 2; ++i) {
@@ -81,13 +86,13 @@ std::map<int, KernErr> g_kerr;
 
 }  // namespace
 
-// The device's word (allocated and zeroed on first use, synchronously), or nullptr.
+// The device's word (allocated and zeroed on first use: zero when this returns, whatever stream renders next), or nullptr.
 uint32_t* kerr_word(int device) {
     std::lock_guard<std::mutex> lk(g_kerr_mu);
     KernErr& k = g_kerr[device];
     if (!k.d.ptr) {
         if (k.d.reserve(rtxd::KERR_WORDS * sizeof(uint32_t)) != hipSuccess) return nullptr;
-        if (hipMemset(k.d.ptr, 0, k.d.bytes) != hipSuccess) k.d.release();
+        if (zero_now(k.d.ptr, k.d.bytes) != hipSuccess) k.d.release();
     }
     return k.d.as<uint32_t>();
 }
