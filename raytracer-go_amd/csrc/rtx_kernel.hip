@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <type_traits>
 
 #include "rtx_device.h"
 #include "rtx_kernel.h"
@@ -1138,8 +1139,6 @@ inline void launch_reduce(const Params& p, const SampleRange& rg, uint64_t slots
 // ------------------------------------------------------------------------------------
 constexpr uint32_t LDS_MAX_BYTES = 64 * 1024;
 
-// v3: chunks of p.kn samples (the scratch holds one chunk), each rendered by a
-// resident-capacity grid of render_items and summed into p.out by reduce_samples.
 // Samples per unit: 8, or fewer when that leaves under 8 units per resident wave (a small
 // image's last units would run on a near-empty GPU).  Measured at 100 spp: 1920x1080 8 -1.6 % vs
 // 16; 400x225 2 -42 % vs 16; Cornell 600x600 8 -3 % vs 16.  16 when that still leaves >= 64
@@ -1147,9 +1146,8 @@ constexpr uint32_t LDS_MAX_BYTES = 64 * 1024;
 // 4 instead of 2 below 8 units of 8 samples per resident wave: the tiered walk (C1 400x225x100: 1.68 ms against 1.77 at
 // 2 and 1.77 at 8; profiles/r05_unit_sweep.jsonl), and since round 6 every render (quadDemo 400x225x100: 0.60 ms
 // against 0.99 at 2, perlinDemo 3.31 against 3.33; profiles/r06_demo_knobs.jsonl).
-inline uint32_t unit_samples(uint64_t tiles, uint32_t kn, int waves, int per_cu, int cus, bool tiered = false) {
+inline uint32_t unit_samples(uint64_t tiles, uint32_t kn, int waves, int per_cu, int cus) {
     const uint64_t per_wave = tiles * kn / (8ull * waves * (uint64_t)per_cu * cus);
-    (void)tiered;
     if (per_wave >= 2 && per_wave < 8) return 4u;
     return per_wave >= 128 ? RTX_SUB_MAX : (per_wave >= 8 ? 8u : (per_wave >= 4 ? 4u : (per_wave >= 2 ? 2u : 1u)));
 }
@@ -1163,30 +1161,11 @@ hipError_t resident_grid(const void* kern, int block, size_t shmem, int* per_cu,
     return e;
 }
 
-// v3: chunks of p.kn samples (the scratch holds one chunk), each rendered by a
-// resident-capacity grid of render_items and summed into p.out by reduce_samples.
-// POOL (a scene in the LDS copy, the timed kernel): the camera-ray pool after the scene copy (render_items<POOL>).
-template <bool COUNT, bool QUADS, bool NOISE, int WAVES = 8, int MINW = 0, bool CLK = false, bool POOL = false,
-          bool ST = false>
-hipError_t launch_items(Params p, bool use_lds, hipStream_t stream, const SampleRange& rg) {
-    // a scene too big for LDS: its top levels (p.n_hot entries) cached in LDS when the
-    // device layout stored them first (RTX_HOT_ENTRIES=0 turns that off)
-    const bool hyb = !use_lds && p.n_hot > 0 && !NOISE;
-    const size_t shmem = POOL ? (size_t)pool_f4_offset(p) * 16 + WAVES * POOL_BYTES_PER_WAVE
-                              : use_lds ? lds_fixed_bytes(p.n_entries, p.n_quads, p.n_materials, p.n_textures)
-                                        : (hyb ? lds_hot_bytes(p.n_hot) : 0);
-    // (an adaptive pass of an accumulator: the ADAPT instantiation of the same kernel)
-#define RTX_ITEMS(...) (p.tile_list ? render_items<__VA_ARGS__, true> : render_items<__VA_ARGS__, false>)
-    const auto kern = POOL      ? RTX_ITEMS(COUNT, true, QUADS, NOISE, WAVES, MINW, false, CLK, 0, POOL, ST)
-                      : use_lds ? RTX_ITEMS(COUNT, true, QUADS, NOISE, WAVES, MINW, false, CLK, 0, false, ST)
-                                : (hyb ? RTX_ITEMS(COUNT, false, QUADS, NOISE, WAVES, MINW, !NOISE, CLK, 0, false, ST)
-                                       : RTX_ITEMS(COUNT, false, QUADS, NOISE, WAVES, MINW, false, CLK, 0, false, ST));
-#undef RTX_ITEMS
-    constexpr int block = 64 * WAVES;
-    int cus = 0, per_cu = 0;
-    hipError_t e = resident_grid((const void*)kern, block, shmem, &per_cu, &cus);
-    if (e != hipSuccess) return e;
-    // the samples [rg.first, end) of this call: a whole render, or one pass of an accumulator
+// v3: the samples [rg.first, rg.first + rg.count) (a whole render, or one pass of an accumulator) in chunks of p.kn (the
+// scratch holds one chunk), each rendered by resident-capacity grids (launch(units, first chunk?): its kernels over the units
+// of p.sub samples: the caller's, or unit_samples for per_cu workgroups of `waves` waves) and summed by launch_reduce.
+template <class Launch>
+hipError_t for_chunks(Params& p, const SampleRange& rg, int waves, int per_cu, int cus, hipStream_t stream, Launch&& launch) {
     const uint64_t end = (uint64_t)rg.first + rg.count;
     const uint32_t chunk = p.kn, sub = p.sub;
     const uint64_t tiles = (uint64_t)tiles_x_of(p.width, p.tile_w_log2) * tiles_y_of(p.rows, p.tile_w_log2);
@@ -1194,32 +1173,105 @@ hipError_t launch_items(Params p, bool use_lds, hipStream_t stream, const Sample
     for (uint64_t k0 = rg.first; k0 < end; k0 += chunk) {
         p.k0 = (uint32_t)k0;  // absolute: the Philox key is k, the scratch index k - k0
         p.kn = end - k0 < chunk ? (uint32_t)(end - k0) : chunk;
-        if (sub == 0) p.sub = unit_samples(tiles, p.kn, WAVES, per_cu, cus);
-        const uint64_t units = tiles * ((p.kn + p.sub - 1) / p.sub);
-        uint64_t blocks = (uint64_t)per_cu * cus;
-        if (blocks > (units + WAVES - 1) / WAVES) blocks = (units + WAVES - 1) / WAVES;  // no wave starts idle
+        p.sub = sub ? sub : unit_samples(tiles, p.kn, waves, per_cu, cus);
+        hipError_t e = launch(tiles * ((p.kn + p.sub - 1) / p.sub), k0 == rg.first);
+        if (e != hipSuccess) return e;
+        launch_reduce(p, rg, slots, k0 + p.kn >= end, stream);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+// A resident grid of per_cu workgroups of `waves` waves on every CU, cut to the chunk's units: no wave starts idle.
+inline uint64_t grid_blocks(uint64_t units, int waves, int per_cu, int cus) {
+    const uint64_t need = (units + waves - 1) / waves, blocks = (uint64_t)per_cu * cus;
+    return blocks < need ? blocks : need;
+}
+
+#ifndef RTX_HYB_WAVES  // the same for scenes in HBM with an 80 KB LDS cache of their most-read entries
+#define RTX_HYB_WAVES 12
+#define RTX_HYB_MINW 6
+#endif
+#ifndef RTX_V3_WAVES  // workgroup size and waves per SIMD of the default v3 kernel (A/B builds override)
+#define RTX_V3_WAVES 8
+#define RTX_V3_MINW 6
+#endif
+
+// Where a launch's kernels read the scene: decided at run time (launch_render) and lifted to a template argument, so
+// that a launcher instantiation names only its placement's kernels.  POOL: the LDS copy, the waves' camera-ray pools after
+// it; LDS: the LDS copy; CACHE12 / CACHE: HBM with the hot entries cached in LDS, past a third of the CU (n_hot >
+// HOT_ENTRIES_8W, and every tiered walk) / up to it; HBM.  POOL and CACHE12: 12-wave workgroups, two per CU.
+enum class Place { POOL, LDS, CACHE12, CACHE, HBM };
+constexpr bool in_lds(Place pl) { return pl == Place::POOL || pl == Place::LDS; }
+constexpr bool cached(Place pl) { return pl == Place::CACHE12 || pl == Place::CACHE; }
+// Waves per workgroup and per SIMD (__launch_bounds__) of a placement's kernels.  `four`: RTX_ITEM_WAVES=4 (A/B: 4 waves per
+// LDS copy of the scene).  6 waves per SIMD: at most 80 VGPRs (the allocation granule is 8); unbound: counting, noise, four.
+constexpr int waves_of(Place pl, bool noise = false, bool four = false) {
+    return noise ? 8 : four ? 4 : pl == Place::POOL ? RTX_POOL_WAVES : pl == Place::CACHE12 ? RTX_HYB_WAVES : RTX_V3_WAVES;
+}
+constexpr int minw_of(Place pl, bool count, bool noise = false, bool four = false) {
+    if (count || noise || four) return 0;
+    return pl == Place::POOL ? RTX_POOL_MINW : pl == Place::CACHE12 ? RTX_HYB_MINW : RTX_V3_MINW;
+}
+// LDS bytes of a launch of `waves` waves: the fixed layout's whole scene (and the waves' pools), the hot entries, or none.
+inline size_t items_shmem(Place pl, const Params& p, int waves) {
+    if (pl == Place::POOL) return (size_t)pool_f4_offset(p) * 16 + waves * POOL_BYTES_PER_WAVE;
+    if (pl == Place::LDS) return lds_fixed_bytes(p.n_entries, p.n_quads, p.n_materials, p.n_textures);
+    return cached(pl) ? lds_hot_bytes(p.n_hot) : 0;
+}
+// lift(f, a, b, ...): f(A{}, B{}, ...) with std::true_type / std::false_type for the run-time booleans a, b, ...; lift_place
+// the same with a std::integral_constant<Place, pl> first.  The one place where a run-time fact becomes a template argument:
+// the generic lambda f excludes a combination that must not exist by `if constexpr` (nothing is instantiated for it).
+template <class F> auto lift(F&& f) { return f(); }
+template <class F, class... Bs>
+auto lift(F&& f, bool b, Bs... rest) {
+    return b ? lift([&](auto... t) { return f(std::true_type{}, t...); }, rest...)
+             : lift([&](auto... t) { return f(std::false_type{}, t...); }, rest...);
+}
+template <class F, class... Bs>
+auto lift_place(F&& f, Place pl, Bs... rest) {
+    const auto as = [&](auto place) { return lift([&](auto... t) { return f(place, t...); }, rest...); };
+    if (pl == Place::POOL) return as(std::integral_constant<Place, Place::POOL>{});
+    if (pl == Place::LDS) return as(std::integral_constant<Place, Place::LDS>{});
+    if (pl == Place::CACHE12) return as(std::integral_constant<Place, Place::CACHE12>{});
+    if (pl == Place::CACHE) return as(std::integral_constant<Place, Place::CACHE>{});
+    return as(std::integral_constant<Place, Place::HBM>{});
+}
+// The TIER 0 instantiations there are.  POOL and CACHE12 are the timed and counting kernels' alone (a noise scene, the 4-wave
+// knob and CLK keep their 8- / 4-wave workgroups); NOISE has no LDS cache (HYB); CLK is for the timed kernel, without noise.
+constexpr bool items_exist(Place pl, bool count, bool noise, bool four, bool clk) {
+    if ((noise || four || clk) && (pl == Place::POOL || pl == Place::CACHE12)) return false;
+    return !(noise && (cached(pl) || four)) && !(clk && (count || noise || four));
+}
+// A render without tiers: one render_items kernel (TIER 0).  Place::POOL: the camera-ray pool after the scene copy.
+template <Place PL, bool COUNT, bool QUADS, bool NOISE, bool FOUR, bool CLK, bool ST>
+hipError_t launch_items(Params p, hipStream_t stream, const SampleRange& rg) {
+    static_assert(items_exist(PL, COUNT, NOISE, FOUR, CLK));
+    constexpr int WAVES = waves_of(PL, NOISE, FOUR), MINW = minw_of(PL, COUNT, NOISE, FOUR), block = 64 * WAVES;
+    const size_t shmem = items_shmem(PL, p, WAVES);
+    const auto kern = lift([](auto adapt) {  // (an adaptive pass of an accumulator: the ADAPT instantiation)
+        return &render_items<COUNT, in_lds(PL), QUADS, NOISE, WAVES, MINW, cached(PL), CLK, 0, PL == Place::POOL, ST, adapt()>;
+    }, p.tile_list != nullptr);
+    int cus = 0, per_cu = 0;
+    if (const hipError_t e = resident_grid((const void*)kern, block, shmem, &per_cu, &cus); e != hipSuccess) return e;
+    return for_chunks(p, rg, WAVES, per_cu, cus, stream, [&](uint64_t units, bool) {
+        const uint64_t blocks = grid_blocks(units, WAVES, per_cu, cus);
         if (p.debug_launch) {
             fprintf(stderr, "rtx v3: waves/wg %d, wgs/CU %d, CUs %d, grid %llu, sub %u, units %llu, lds %zu B\n", WAVES,
                     per_cu, cus, (unsigned long long)blocks, p.sub, (unsigned long long)units, shmem);
             print_launch_name((const void*)kern);
         }
-        e = hipMemsetAsync(p.tile_counter, 0, sizeof(uint32_t), stream);  // (the watchdog flag: once per render)
-        if (e != hipSuccess) return e;
+        const hipError_t em = hipMemsetAsync(p.tile_counter, 0, sizeof(uint32_t), stream);  // (the watchdog flag: once per render)
+        if (em != hipSuccess) return em;
         hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(block), shmem, stream, p);
-        launch_reduce(p, rg, slots, k0 + p.kn >= end, stream);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        return hipSuccess;
+    });
 }
 
-// LDS bytes of a render_items launch: the fixed layout's whole scene (USE_LDS), the hot entries of a
-// scene in HBM (HYB), or none.
-inline size_t items_shmem(const Params& p, bool use_lds, bool hyb) {
-    return use_lds ? lds_fixed_bytes(p.n_entries, p.n_quads, p.n_materials, p.n_textures)
-                   : (hyb ? lds_hot_bytes(p.n_hot) : 0);
+// The launch_tiered instantiations there are.  Every tiered walk with LDS caches has the 12-wave workgroups; CLK is for
+// the timed kernels of scenes in the LDS copy; quads are for single-row shards (no ST) and have no CLK kernels.
+constexpr bool tiered_exist(Place pl, bool count, bool clk, bool st, bool quads) {
+    return pl != Place::CACHE && !(quads && (st || clk)) && !(clk && (count || !in_lds(pl)));
 }
-
 // The tiered walk of a sphere scene whose near and far layouts are placed alike —
 // both in the LDS copy (USE_LDS), both in HBM with an LDS cache of their hot entries (HYB), or both
 // in HBM: per chunk the near pass (pn), the far pass over its queue (pf), the redo pass over the
@@ -1227,17 +1279,20 @@ inline size_t items_shmem(const Params& p, bool use_lds, bool hyb) {
 // POOL: the near pass takes its camera rays from the waves' LDS pools (render_items<POOL>), in
 // workgroups of WN waves (12: two per CU, each with its scene copy and 12 pools); the far and redo
 // passes keep WAVES.
-template <bool COUNT, int WAVES, int MINW, bool CLK = false, bool USE_LDS = true, bool HYB = false, bool POOL = false,
-          bool ST = false, bool QUADS = false, int WN = POOL ? RTX_POOL_WAVES : WAVES>
+template <Place PL, bool COUNT, bool CLK, bool ST, bool QUADS>
 hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream, const SampleRange& rg) {
-    constexpr int MN = POOL && MINW ? RTX_POOL_MINW : MINW;  // the near (and drain) kernel's waves per SIMD
-    const bool adapt = pn.tile_list != nullptr;  // an adaptive pass: the near pass's (and the drain's) ADAPT instantiation
-    const auto kn = adapt ? render_items<COUNT, USE_LDS, QUADS, false, WN, MN, HYB, CLK, 1, POOL, ST, true>
-                          : render_items<COUNT, USE_LDS, QUADS, false, WN, MN, HYB, CLK, 1, POOL, ST, false>;
-    const auto kf = render_items<COUNT, USE_LDS, QUADS, false, WAVES, MINW, HYB, CLK, 2>;  // (rows from the records)
-    const auto kr = render_items<COUNT, USE_LDS, QUADS, false, WAVES, MINW, HYB, false, 3, false, ST>;
-    const size_t sn = POOL ? (size_t)pool_f4_offset(pn) * 16 + WN * POOL_BYTES_PER_WAVE : items_shmem(pn, USE_LDS, HYB),
-                 sf = items_shmem(pf, USE_LDS, HYB);
+    static_assert(tiered_exist(PL, COUNT, CLK, ST, QUADS));
+    constexpr bool USE_LDS = in_lds(PL), HYB = cached(PL), POOL = PL == Place::POOL, NOISE = false;
+    constexpr Place PF = POOL ? Place::LDS : PL;  // the far and redo passes: the near pass's placement without the pools
+    constexpr int WN = waves_of(PL), MN = minw_of(PL, COUNT), WAVES = waves_of(PF), MINW = minw_of(PF, COUNT);
+    constexpr bool REDO_CLK = false, REDO_POOL = false;  // (the redo pass has no CLK and no pooled instantiation)
+    const bool adaptive = pn.tile_list != nullptr;  // an adaptive pass: the near pass's (and the drain's) ADAPT instantiation
+    const auto kn = lift([](auto adapt) {
+        return &render_items<COUNT, USE_LDS, QUADS, NOISE, WN, MN, HYB, CLK, 1, POOL, ST, adapt()>;
+    }, adaptive);
+    const auto kf = render_items<COUNT, USE_LDS, QUADS, NOISE, WAVES, MINW, HYB, CLK, 2>;  // (rows from the records)
+    const auto kr = render_items<COUNT, USE_LDS, QUADS, NOISE, WAVES, MINW, HYB, REDO_CLK, 3, REDO_POOL, ST>;
+    const size_t sn = items_shmem(PL, pn, WN), sf = items_shmem(PF, pf, WAVES);
     constexpr int block = 64 * WAVES, block_n = 64 * WN;
     int cus = 0, per_n = 0, per_f = 0, per_r = 0;
     hipError_t e = resident_grid((const void*)kn, block_n, sn, &per_n, &cus);
@@ -1250,8 +1305,7 @@ hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream, const SampleR
     constexpr bool CAN_DRAIN = !COUNT && !CLK && !HYB;
     void (*kdrain)(DrainArgs) = nullptr;
     if constexpr (CAN_DRAIN)
-        kdrain = adapt ? render_drain<USE_LDS, WN, MN, HYB, POOL, ST, QUADS, true>
-                       : render_drain<USE_LDS, WN, MN, HYB, POOL, ST, QUADS, false>;
+        kdrain = lift([](auto adapt) { return &render_drain<USE_LDS, WN, MN, HYB, POOL, ST, QUADS, adapt()>; }, adaptive);
     const void* kd = (const void*)kdrain;
     // (the drain's two per-workgroup words in LDS after the larger layout)
     const size_t sl = ((sn > sf ? sn : sf) + 15) / 16 * 16, sd = sl + 16;
@@ -1260,24 +1314,14 @@ hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream, const SampleR
     bool drain = CAN_DRAIN && pn.drain && pn.drain_count;
     if (drain && (e = resident_grid(kd, block_n, sd, &per_d, &cus)) != hipSuccess) return e;
     drain = drain && per_d >= per_n;
-    const uint64_t end = (uint64_t)rg.first + rg.count;  // (launch_items)
-    const uint32_t chunk = pn.kn, sub = pn.sub;
-    const uint64_t tiles = (uint64_t)tiles_x_of(pn.width, pn.tile_w_log2) * tiles_y_of(pn.rows, pn.tile_w_log2);
-    const uint64_t slots = tiles * 64;
     Params pr = pf;  // the redo pass: the far layout over the chunk's units, flagged samples only
     pr.tier = 0;
     // the far and redo passes' unit queue heads: words of their own, zeroed with the chunk's others (chunk_start)
     pf.tile_counter = pn.drain_count + DRAIN_WORDS - 2;
     pr.tile_counter = pn.drain_count + DRAIN_WORDS - 1;
-    for (uint64_t k0 = rg.first; k0 < end; k0 += chunk) {
-        pn.k0 = pf.k0 = pr.k0 = (uint32_t)k0;
-        pn.kn = pf.kn = pr.kn = end - k0 < chunk ? (uint32_t)(end - k0) : chunk;
-        pn.sub = sub ? sub : unit_samples(tiles, pn.kn, WN, per_n, cus, true);
-        pf.sub = pr.sub = pn.sub;
-        const uint64_t units = tiles * ((pn.kn + pn.sub - 1) / pn.sub);
-        uint64_t bn = (uint64_t)per_n * cus, br = (uint64_t)per_r * cus;
-        if (bn > (units + WN - 1) / WN) bn = (units + WN - 1) / WN;
-        if (br > (units + WAVES - 1) / WAVES) br = (units + WAVES - 1) / WAVES;
+    return for_chunks(pn, rg, WN, per_n, cus, stream, [&](uint64_t units, bool first) {
+        pf.k0 = pr.k0 = pn.k0, pf.kn = pr.kn = pn.kn, pf.sub = pr.sub = pn.sub;  // (for_chunks set the near pass's)
+        const uint64_t bn = grid_blocks(units, WN, per_n, cus), br = grid_blocks(units, WAVES, per_r, cus);
         if (pn.debug_launch)
             fprintf(stderr, "rtx tiered: waves/wg %d / %d, wgs/CU %d / %d / %d, grid %llu, sub %u, units %llu, lds %zu / %zu B, "
                     "cap %u, camera-ray pool %d, drain %d\n", WN, WAVES, per_n, per_f, per_r, (unsigned long long)bn, pn.sub,
@@ -1295,7 +1339,7 @@ hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream, const SampleR
             }
             print_launch_name((const void*)kr);
         }
-        hipLaunchKernelGGL(chunk_start, dim3(1), dim3(256), 0, stream, pn, (uint32_t)(k0 == rg.first));
+        hipLaunchKernelGGL(chunk_start, dim3(1), dim3(256), 0, stream, pn, (uint32_t)first);
         if (drain_now) {
             pn.drain_region = pf.drain_region = pn.defer_cap / (uint32_t)bn;
             if constexpr (CAN_DRAIN)
@@ -1306,38 +1350,8 @@ hipError_t launch_tiered(Params pn, Params pf, hipStream_t stream, const SampleR
         }
         hipLaunchKernelGGL(spill_redo_list, dim3((uint32_t)cus * 4), dim3(256), 0, stream, pn);
         hipLaunchKernelGGL(kr, dim3((uint32_t)br), dim3(block), sf, stream, pr);
-        launch_reduce(pn, rg, slots, k0 + pn.kn >= end, stream);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-#ifndef RTX_HYB_WAVES  // the same for scenes in HBM with an 80 KB LDS cache of their most-read entries
-#define RTX_HYB_WAVES 12
-#define RTX_HYB_MINW 6
-#endif
-#ifndef RTX_V3_WAVES  // workgroup size and waves per SIMD of the default v3 kernel (A/B builds override)
-#define RTX_V3_WAVES 8
-#define RTX_V3_MINW 6
-#endif
-
-template <bool COUNT, bool ST>
-hipError_t launch_items_for(const Params& p, bool use_lds, hipStream_t stream, const SampleRange& rg) {
-    if (p.has_noise) return p.n_quads ? launch_items<COUNT, true, true, 8, 0, false, false, ST>(p, use_lds, stream, rg)
-                                      : launch_items<COUNT, false, true, 8, 0, false, false, ST>(p, use_lds, stream, rg);
-    if (p.item_waves == 4)  // A/B: 4 waves per LDS copy of the scene
-        return p.n_quads ? launch_items<COUNT, true, false, 4, 0, false, false, ST>(p, use_lds, stream, rg)
-                         : launch_items<COUNT, false, false, 4, 0, false, false, ST>(p, use_lds, stream, rg);
-    // 6 waves per SIMD: at most 80 VGPRs (the allocation granule is 8)
-    constexpr int MV = COUNT ? 0 : RTX_V3_MINW, MH = COUNT ? 0 : RTX_HYB_MINW, MP = COUNT ? 0 : RTX_POOL_MINW;
-    if (!use_lds && p.n_hot > HOT_ENTRIES_8W)  // an LDS cache past a third of the CU: 12-wave workgroups, two per CU
-        return p.n_quads ? launch_items<COUNT, true, false, RTX_HYB_WAVES, MH, false, false, ST>(p, use_lds, stream, rg)
-                         : launch_items<COUNT, false, false, RTX_HYB_WAVES, MH, false, false, ST>(p, use_lds, stream, rg);
-    if (use_lds && pool_fits(p))  // the camera-ray pool (12-wave workgroups, two per CU) when the scene copy leaves room
-        return p.n_quads ? launch_items<COUNT, true, false, RTX_POOL_WAVES, MP, false, true, ST>(p, use_lds, stream, rg)
-                         : launch_items<COUNT, false, false, RTX_POOL_WAVES, MP, false, true, ST>(p, use_lds, stream, rg);
-    return p.n_quads ? launch_items<COUNT, true, false, RTX_V3_WAVES, MV, false, false, ST>(p, use_lds, stream, rg)
-                     : launch_items<COUNT, false, false, RTX_V3_WAVES, MV, false, false, ST>(p, use_lds, stream, rg);
+        return hipSuccess;
+    });
 }
 
 uint32_t scene_placement(const Params& p, uint32_t flags) {
@@ -1354,63 +1368,45 @@ uint32_t tier_placement(const Params& near, const Params& far, uint32_t flags) {
     return a == b ? a : RTX_SCENE_IN_HBM;  // placed unalike: both passes read their layouts from HBM
 }
 
-// ST: the render's shard is striped (Params::stripe_log2 > 0): every kernel's ST instantiation (render_items).
-template <bool ST>
-hipError_t launch_render_t(const Params& p, uint32_t flags, hipStream_t stream, const Params* far, const SampleRange& rg) {
-    const bool count = (flags & RTX_FLAG_COUNTERS) != 0;
-    if (far) {  // the caller checked: spheres only, both layouts placed alike (tier_placement), no noise
-        const uint32_t place = tier_placement(p, *far, flags);
-        if (p.tier != 1 || far->tier != 2 || !p.defer || !far->defer || !p.redo_bits || p.has_noise)
-            return hipErrorInvalidValue;
-        if (p.n_quads) {  // quads: single-row shards, the timed and counting kernels (rtx_capi's enqueue_on)
-            if (ST || (!count && (flags & RTX_FLAG_TIMING))) return hipErrorInvalidValue;
-            if constexpr (!ST) {
-                constexpr int V = RTX_V3_WAVES, MV = RTX_V3_MINW, H = RTX_HYB_WAVES, MH = RTX_HYB_MINW;
-                if (place == RTX_SCENE_IN_LDS) {
-                    const bool pool = pool_fits(p);
-                    if (count) return pool ? launch_tiered<true, V, 0, false, true, false, true, false, true>(p, *far, stream, rg)
-                                           : launch_tiered<true, V, 0, false, true, false, false, false, true>(p, *far, stream, rg);
-                    return pool ? launch_tiered<false, V, MV, false, true, false, true, false, true>(p, *far, stream, rg)
-                                : launch_tiered<false, V, MV, false, true, false, false, false, true>(p, *far, stream, rg);
-                }
-                if (place == RTX_SCENE_LDS_CACHE)
-                    return count ? launch_tiered<true, H, 0, false, false, true, false, false, true>(p, *far, stream, rg)
-                                 : launch_tiered<false, H, MH, false, false, true, false, false, true>(p, *far, stream, rg);
-                return count ? launch_tiered<true, V, 0, false, false, false, false, false, true>(p, *far, stream, rg)
-                             : launch_tiered<false, V, MV, false, false, false, false, false, true>(p, *far, stream, rg);
-            }
-        }
-        const bool clk = !count && (flags & RTX_FLAG_TIMING);  // diagnostics: the wave-cycle split of the passes
-        constexpr int V = RTX_V3_WAVES, MV = RTX_V3_MINW, H = RTX_HYB_WAVES, MH = RTX_HYB_MINW;
-        if (place == RTX_SCENE_IN_LDS) {
-            const bool pool = pool_fits(p);  // (the counting kernel too: its schedule counters are the timed kernel's)
-            if (clk) return pool ? launch_tiered<false, V, MV, true, true, false, true, ST>(p, *far, stream, rg)
-                                 : launch_tiered<false, V, MV, true, true, false, false, ST>(p, *far, stream, rg);
-            if (count) return pool ? launch_tiered<true, V, 0, false, true, false, true, ST>(p, *far, stream, rg)
-                                   : launch_tiered<true, V, 0, false, true, false, false, ST>(p, *far, stream, rg);
-            return pool ? launch_tiered<false, V, MV, false, true, false, true, ST>(p, *far, stream, rg)
-                        : launch_tiered<false, V, MV, false, true, false, false, ST>(p, *far, stream, rg);
-        }
-        if (place == RTX_SCENE_LDS_CACHE)  // both cached in LDS (tier_placement): 12-wave workgroups, two per CU
-            return count ? launch_tiered<true, H, 0, false, false, true, false, ST>(p, *far, stream, rg)
-                         : launch_tiered<false, H, MH, false, false, true, false, ST>(p, *far, stream, rg);
-        return count ? launch_tiered<true, V, 0, false, false, false, false, ST>(p, *far, stream, rg)
-                     : launch_tiered<false, V, MV, false, false, false, false, ST>(p, *far, stream, rg);
-    }
-    const bool use_lds = scene_placement(p, flags) == RTX_SCENE_IN_LDS;
-    if (!count && (flags & RTX_FLAG_TIMING) && !p.has_noise && p.item_waves != 4)  // diagnostics: sphere scenes
-        return p.n_quads ? launch_items<false, true, false, RTX_V3_WAVES, RTX_V3_MINW, true, false, ST>(p, use_lds, stream, rg)
-                         : launch_items<false, false, false, RTX_V3_WAVES, RTX_V3_MINW, true, false, ST>(p, use_lds, stream, rg);
-    return count ? launch_items_for<true, ST>(p, use_lds, stream, rg) : launch_items_for<false, ST>(p, use_lds, stream, rg);
-}
-
+// The run-time decisions of a render, each lifted to its template argument once (lift_place): the placement, counting,
+// CLK, quads, a striped shard (Params::stripe_log2 > 0: every kernel's ST instantiation), and without tiers a noise scene
+// and the 4-wave knob.
 hipError_t launch_render(const Params& p, uint32_t flags, hipStream_t stream, const Params* far, const SampleRange* pass) {
     if (p.width == 0 || p.rows == 0) return hipSuccess;
     if (!p.scratch) return hipErrorInvalidValue;  // the caller sizes the sample scratch
     if (pass && (!pass->s || !pass->q || pass->count == 0 || pass->first + pass->count < pass->first))
         return hipErrorInvalidValue;
     const SampleRange rg = pass ? *pass : SampleRange{0u, p.cam.samples_per_pixel, nullptr, nullptr};
-    return p.stripe_log2 ? launch_render_t<true>(p, flags, stream, far, rg) : launch_render_t<false>(p, flags, stream, far, rg);
+    const bool count = (flags & RTX_FLAG_COUNTERS) != 0, quads = p.n_quads != 0, striped = p.stripe_log2 != 0;
+    const bool timing = !count && (flags & RTX_FLAG_TIMING);  // diagnostics: the wave-cycle split of the passes
+    if (far) {  // the caller checked: both layouts placed alike (tier_placement), no noise
+        const uint32_t both = tier_placement(p, *far, flags);
+        if (p.tier != 1 || far->tier != 2 || !p.defer || !far->defer || !p.redo_bits || p.has_noise)
+            return hipErrorInvalidValue;
+        // quads: single-row shards, the timed and counting kernels (rtx_capi's enqueue_on)
+        if (quads && (striped || timing)) return hipErrorInvalidValue;
+        // the camera-ray pool when the scene copy leaves room (the counting kernel too: its schedule counters are the
+        // timed kernel's); both cached in LDS (tier_placement): 12-wave workgroups, two per CU
+        const Place place = both == RTX_SCENE_IN_LDS ? (pool_fits(p) ? Place::POOL : Place::LDS)
+                                                     : (both == RTX_SCENE_LDS_CACHE ? Place::CACHE12 : Place::HBM);
+        return lift_place([&](auto pl, auto cnt, auto clk, auto st, auto qd) {
+            if constexpr (!tiered_exist(pl(), cnt(), clk(), st(), qd())) return hipErrorInvalidValue;  // (never: see above)
+            else return launch_tiered<pl(), cnt(), clk(), st(), qd()>(p, *far, stream, rg);
+        }, place, count, timing && both == RTX_SCENE_IN_LDS, striped, quads);
+    }
+    const bool use_lds = scene_placement(p, flags) == RTX_SCENE_IN_LDS;
+    const bool noise = p.has_noise, four = !noise && p.item_waves == 4;  // A/B: 4 waves per LDS copy of the scene
+    const bool clk = timing && !noise && !four, wide = !noise && !four && !clk;
+    // wide, the 12-wave workgroups, two per CU: the camera-ray pool when the scene copy leaves room, and an LDS cache past
+    // a third of the CU.  A scene too big for LDS: its top levels (p.n_hot entries) cached in LDS when the device layout
+    // stored them first (RTX_HOT_ENTRIES=0 turns that off)
+    const Place place = use_lds                 ? (wide && pool_fits(p) ? Place::POOL : Place::LDS)
+                        : p.n_hot > 0 && !noise ? (wide && p.n_hot > HOT_ENTRIES_8W ? Place::CACHE12 : Place::CACHE)
+                                                : Place::HBM;
+    return lift_place([&](auto pl, auto cnt, auto qd, auto nz, auto fr, auto ck, auto st) {
+        if constexpr (!items_exist(pl(), cnt(), nz(), fr(), ck())) return hipErrorInvalidValue;  // (never: see above)
+        else return launch_items<pl(), cnt(), qd(), nz(), fr(), ck(), st()>(p, stream, rg);
+    }, place, count, quads, noise, four, clk, striped);
 }
 
 }  // namespace rtxd

@@ -11,7 +11,8 @@ evidence that it did work.
                               them).  With RTX_DEBUG_LAUNCH=1 every launch prints "rtx launch: <mangled name>"; the
                               child attributes the names to the call that launched them and to that call's rtx_stats.
   test_every_reachable_kernel_ran   the names seen with evidence are the list minus UNREACHABLE, and no name of
-                              UNREACHABLE was ever launched.
+                              UNREACHABLE was ever launched.  UNREACHABLE is empty: the dispatch compiles no kernel it
+                              cannot launch, so every listed kernel is seen with evidence.
 
 Evidence, per kernel class (the call's own stats; the call belongs to a combination all of whose checks passed):
   TIER 0            the image is the oracle's
@@ -75,28 +76,10 @@ def listed() -> list:
         return [ln.split("\t")[0] for ln in f.read().splitlines() if ln and not ln.startswith("#")]
 
 
-def _unreachable() -> dict:
-    """launch_items names four kernels per template set and picks one at run time.  The 12-wave sets are entered with
-    the choice already made, so two of their four are never picked: 32 kernels (COUNT x QUADS x ST x ADAPT x 2)."""
-    lds = ("launch_items<..., WAVES = 12>: its POOL = false set is entered only from launch_items_for's "
-           "`if (!use_lds && p.n_hot > HOT_ENTRIES_8W)` (use_lds is false, so `use_lds ? RTX_ITEMS(COUNT, true, ...)` is "
-           "not taken) and its POOL = true set picks `POOL ? RTX_ITEMS(..., POOL, ST)` first: the 12-wave kernel with the "
-           "scene's LDS copy and no camera-ray pool is never launched.")
-    hbm = ("launch_items<..., WAVES = 12>: entered from launch_items_for's `if (!use_lds && p.n_hot > HOT_ENTRIES_8W)`, "
-           "where n_hot > 0 and NOISE is false, so `hyb = !use_lds && p.n_hot > 0 && !NOISE` is true and the HYB kernel is "
-           "picked (the POOL = true set picks its pooled kernel first): the 12-wave kernel reading HBM without the LDS "
-           "cache is never launched.")
-    out = {}
-    for count, quads, st, adapt in itertools.product((0, 1), repeat=4):
-        common = dict(COUNT=count, QUADS=quads, NOISE=0, WAVES=12, MINW=0 if count else 6, CLK=0, TIER=0, POOL=0, ST=st,
-                      ADAPT=adapt)
-        out[items_name(USE_LDS=1, HYB=0, **common)] = lds
-        out[items_name(USE_LDS=0, HYB=0, **common)] = hbm
-    return out
-
-
-# kernel name -> the dispatch condition that excludes it for every scene, flag, region and environment knob
-UNREACHABLE = _unreachable()
+# kernel name -> the dispatch condition that excludes it for every scene, flag, region and environment knob.  Empty: the
+# launchers take the placement as a template argument and name only the kernels they launch, so every
+# listed kernel needs evidence.  (items_name builds a name for a future entry.)
+UNREACHABLE = {}
 
 
 # ---- the CPU test ---------------------------------------------------------------------------------------------------
