@@ -13,12 +13,16 @@
 // lane outside the image leaves at once.
 #include "rtx_denoise_pixel.h"
 #include "rtx_guides.h"
+#include "rtx_launch_name.h"
 
 namespace rtxd {
 namespace {
 
 constexpr uint32_t DN_W = 64, DN_H = 4;  // a workgroup's pixels: four waves, one 64-pixel row segment each
 
+}  // namespace
+
+// (The kernels: in rtxd itself, not in the unit's anonymous namespace; rtx_trace.hip, trace_rays.)
 __global__ __launch_bounds__(DN_W * DN_H) void denoise_prepare(const float* __restrict__ rgb, const float* __restrict__ var,
                                                                 const float4* __restrict__ guides, uint32_t width,
                                                                 uint32_t rows, float4* __restrict__ cv) {
@@ -42,8 +46,6 @@ __global__ __launch_bounds__(DN_W * DN_H) void atrous_level(const float4* __rest
     else dst[i] = c;
 }
 
-}  // namespace
-
 hipError_t launch_denoise(const DenoiseArgs& a, hipStream_t stream) {
     const uint64_t P = (uint64_t)a.width * a.rows;
     if (P == 0) return hipSuccess;
@@ -54,9 +56,11 @@ hipError_t launch_denoise(const DenoiseArgs& a, hipStream_t stream) {
     static_assert(sizeof(rtx_guide) == 2 * sizeof(float4), "a guide is two float4: (albedo, cover), (normal, depth)");
     const float4* guides = reinterpret_cast<const float4*>(a.guides);
     float4* buf[2] = {a.work, a.work + P};
+    name_launch(&denoise_prepare);
     hipLaunchKernelGGL(denoise_prepare, grid, block, 0, stream, a.rgb, a.var, guides, a.width, a.rows, buf[0]);
     for (uint32_t i = 0; i < a.params.iterations; ++i) {
         const float4* src = buf[i & 1u];
+        name_launch(i + 1 == a.params.iterations ? &atrous_level<true> : &atrous_level<false>);
         if (i + 1 == a.params.iterations)
             hipLaunchKernelGGL(atrous_level<true>, grid, block, 0, stream, src, guides, a.width, a.rows, 1u << i, a.params,
                                (float4*)nullptr, a.out);

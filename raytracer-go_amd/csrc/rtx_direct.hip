@@ -21,6 +21,7 @@
 // a ballot only sees the lanes that are there.
 #include "rtx_direct.h"
 
+#include "rtx_launch_name.h"
 #include "rtx_trace.h"
 #include "rtx_walk.h"
 
@@ -149,6 +150,9 @@ __device__ __forceinline__ BounceWeight bounce_weight(const float area, const fl
 // The light sample's weight of its own g.
 __device__ __forceinline__ float light_weight(const float g) { return 1.0f / (1.0f + g * g); }
 
+}  // namespace
+
+// The three kernels: in rtxd itself, not in the unit's anonymous namespace (rtx_trace.hip, trace_rays).
 // rtx_emitter_weight_device: a thread per record, 64 records per wave step, no walk and no cross-lane state but the
 // counting instantiation's sum (every lane of a launched wave reaches it).
 template <bool COUNT>
@@ -486,18 +490,17 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void direct_paths(DirectPathParams
     }
 }
 
+namespace {
+
 template <bool QUADS, bool FIXED>
 hipError_t launch_paths_noise(const DirectPathParams& p, bool noise, bool mis, hipStream_t stream) {
     const size_t shmem = FIXED ? walk_lds_bytes(p.scene.n_entries, p.scene.n_quads) : 0;
     const uint64_t tiles = (uint64_t)tiles_x_of(p.shard.width, p.tile_w_log2) * tiles_y_of(p.shard.rows, p.tile_w_log2);
     const dim3 grid((uint32_t)((tiles + WALK_WAVES - 1) / WALK_WAVES)), block(64 * WALK_WAVES);
-    if (mis) {
-        if (noise) hipLaunchKernelGGL((direct_paths<QUADS, FIXED, true, true>), grid, block, shmem, stream, p);
-        else hipLaunchKernelGGL((direct_paths<QUADS, FIXED, false, true>), grid, block, shmem, stream, p);
-    } else {
-        if (noise) hipLaunchKernelGGL((direct_paths<QUADS, FIXED, true, false>), grid, block, shmem, stream, p);
-        else hipLaunchKernelGGL((direct_paths<QUADS, FIXED, false, false>), grid, block, shmem, stream, p);
-    }
+    const auto kern = mis ? (noise ? &direct_paths<QUADS, FIXED, true, true> : &direct_paths<QUADS, FIXED, false, true>)
+                          : (noise ? &direct_paths<QUADS, FIXED, true, false> : &direct_paths<QUADS, FIXED, false, false>);
+    name_launch(kern);
+    hipLaunchKernelGGL(kern, grid, block, shmem, stream, p);
     return hipGetLastError();
 }
 
@@ -506,8 +509,9 @@ hipError_t launch_noise(const DirectParams& p, bool noise, hipStream_t stream) {
     const size_t shmem = FIXED ? walk_lds_bytes(p.scene.n_entries, p.scene.n_quads) : 0;
     const uint64_t waves = ((uint64_t)p.n + p.range - 1) / p.range;
     const dim3 grid((uint32_t)((waves + WALK_WAVES - 1) / WALK_WAVES)), block(64 * WALK_WAVES);
-    if (noise) hipLaunchKernelGGL((direct_lights<COUNT, QUADS, FIXED, true>), grid, block, shmem, stream, p);
-    else hipLaunchKernelGGL((direct_lights<COUNT, QUADS, FIXED, false>), grid, block, shmem, stream, p);
+    const auto kern = noise ? &direct_lights<COUNT, QUADS, FIXED, true> : &direct_lights<COUNT, QUADS, FIXED, false>;
+    name_launch(kern);
+    hipLaunchKernelGGL(kern, grid, block, shmem, stream, p);
     return hipGetLastError();
 }
 
@@ -535,8 +539,9 @@ hipError_t launch_emitter_weights(const EmitterWeightParams& p, bool count, hipS
         (count && !p.counters))
         return hipErrorInvalidValue;
     const dim3 grid((p.n + 255u) / 256u), block(256);
-    if (count) hipLaunchKernelGGL(emitter_weights<true>, grid, block, 0, stream, p);
-    else hipLaunchKernelGGL(emitter_weights<false>, grid, block, 0, stream, p);
+    const auto kern = count ? &emitter_weights<true> : &emitter_weights<false>;
+    name_launch(kern);
+    hipLaunchKernelGGL(kern, grid, block, 0, stream, p);
     return hipGetLastError();
 }
 

@@ -18,6 +18,7 @@
 // its forms return the same bits for every lane that takes the short one.
 #include "rtx_guides.h"
 
+#include "rtx_launch_name.h"
 #include "rtx_trace.h"
 #include "rtx_walk.h"
 
@@ -49,8 +50,11 @@ __device__ __forceinline__ FirstHit first_hit(const GuideParams& p, const SceneR
     return FirstHit{a, h.hit ? h.n : v3(0.0f, 0.0f, 0.0f), t.closest, h.hit};
 }
 
+}  // namespace
+
 // QUADS: the scene holds quads.  FIXED: the scene in the workgroup's LDS copy (scene_ref_fixed), else read from
 // HBM.  NOISE: the scene has a Perlin texture.
+// (In rtxd itself, not in the unit's anonymous namespace: rtx_trace.hip, trace_rays.)
 template <bool QUADS, bool FIXED, bool NOISE>
 __global__ __launch_bounds__(64 * WALK_WAVES) void guide_images(GuideParams p) {
     extern __shared__ float4 lds_entries[];
@@ -116,13 +120,16 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void guide_images(GuideParams p) {
     }
 }
 
+namespace {
+
 template <bool QUADS, bool FIXED>
 hipError_t launch_noise(const GuideParams& p, bool noise, hipStream_t stream) {
     const size_t shmem = FIXED ? walk_lds_bytes(p.scene.n_entries, p.scene.n_quads) : 0;
     const uint64_t tiles = (uint64_t)tiles_x_of(p.shard.width, p.tile_w_log2) * tiles_y_of(p.shard.rows, p.tile_w_log2);
     const dim3 grid((uint32_t)((tiles + WALK_WAVES - 1) / WALK_WAVES)), block(64 * WALK_WAVES);
-    if (noise) hipLaunchKernelGGL((guide_images<QUADS, FIXED, true>), grid, block, shmem, stream, p);
-    else hipLaunchKernelGGL((guide_images<QUADS, FIXED, false>), grid, block, shmem, stream, p);
+    const auto kern = noise ? &guide_images<QUADS, FIXED, true> : &guide_images<QUADS, FIXED, false>;
+    name_launch(kern);
+    hipLaunchKernelGGL(kern, grid, block, shmem, stream, p);
     return hipGetLastError();
 }
 

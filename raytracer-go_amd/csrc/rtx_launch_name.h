@@ -12,6 +12,7 @@
 #include <dlfcn.h>
 
 #include <cstdio>
+#include <cstdlib>
 
 namespace rtxd {
 
@@ -24,5 +25,20 @@ inline const char* kernel_symbol(const void* kern) {
 
 // One "rtx launch:" line; the caller checks Params::debug_launch.
 inline void print_launch_name(const void* kern) { fprintf(stderr, "rtx launch: %s\n", kernel_symbol(kern)); }
+
+// The block launchers (launch_trace, launch_direct, launch_direct_paths, launch_emitter_weights, launch_guides,
+// launch_shade, launch_camera_rays, launch_denoise): their argument structs go to the device as they are and have no
+// debug_launch field, so RTX_DEBUG_LAUNCH is read here, per launch, as env_knob reads it (clamped to 0 / 1).
+inline bool debug_launch_env() {
+    const char* e = std::getenv("RTX_DEBUG_LAUNCH");
+    return e && std::strtol(e, nullptr, 10) >= 1;
+}
+
+// One "rtx launch:" line for the kernel a block launcher is about to launch; tests/test_block_census.py holds the
+// names to tests/block_kernels.txt.
+template <class K>
+inline void name_launch(K* kern) {
+    if (debug_launch_env()) print_launch_name((const void*)kern);
+}
 
 }  // namespace rtxd

@@ -22,6 +22,7 @@
 #include "rtx_shade.h"
 
 #include "rtx_device.h"
+#include "rtx_launch_name.h"
 
 namespace rtxd {
 namespace {
@@ -34,8 +35,11 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     return v;
 }
 
+}  // namespace
+
 // COUNT: the counting instantiation (hits, scattered, rng_draws, texel_fetches).  NOISE: the scene has a Perlin
 // texture.  The body is shade()'s material section (rtx_device.h), per lane.
+// (This kernel and camera_rays: in rtxd itself, not in the unit's anonymous namespace; rtx_trace.hip, trace_rays.)
 template <bool COUNT, bool NOISE>
 __global__ __launch_bounds__(SHADE_BLOCK) void shade_hits(ShadeParams p) {
     const uint32_t i = blockIdx.x * SHADE_BLOCK + threadIdx.x;  // (n <= SHADE_LAUNCH_MAX: no wrap)
@@ -163,11 +167,14 @@ __global__ __launch_bounds__(SHADE_BLOCK) void camera_rays(CameraRayParams p) {
     }
 }
 
+namespace {
+
 template <bool COUNT>
 hipError_t launch_noise(const ShadeParams& p, bool noise, hipStream_t stream) {
     const dim3 grid((p.n + SHADE_BLOCK - 1) / SHADE_BLOCK), block(SHADE_BLOCK);
-    if (noise) hipLaunchKernelGGL((shade_hits<COUNT, true>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((shade_hits<COUNT, false>), grid, block, 0, stream, p);
+    const auto kern = noise ? &shade_hits<COUNT, true> : &shade_hits<COUNT, false>;
+    name_launch(kern);
+    hipLaunchKernelGGL(kern, grid, block, 0, stream, p);
     return hipGetLastError();
 }
 
@@ -188,6 +195,7 @@ hipError_t launch_camera_rays(const CameraRayParams& p, hipStream_t stream) {
     if (P > 0xFFFFFFFFull || sh.kn > CAMERA_LAUNCH_SAMPLES || !p.rays || sh.world == 0 || sh.rank >= sh.world)
         return hipErrorInvalidValue;
     const dim3 grid((uint32_t)((P + SHADE_BLOCK - 1) / SHADE_BLOCK), sh.kn), block(SHADE_BLOCK);
+    name_launch(&camera_rays);
     hipLaunchKernelGGL(camera_rays, grid, block, 0, stream, p);
     return hipGetLastError();
 }

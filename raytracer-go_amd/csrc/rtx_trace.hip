@@ -15,6 +15,7 @@
 // rays are begun and hit records computed on all 64 lanes, and only the selects and stores are per lane.
 #include "rtx_trace.h"
 
+#include "rtx_launch_name.h"
 #include "rtx_walk.h"
 
 namespace rtxd {
@@ -52,9 +53,13 @@ __device__ __forceinline__ void write_hit(const TraceParams& p, const SceneRef E
     }
 }
 
+}  // namespace
+
 // COUNT: the counting instantiation (node_visits, prim_tests, hits).  QUADS: the scene holds quads.  FIXED: the
 // scene in the workgroup's LDS copy (scene_ref_fixed), else read from HBM.  ANY: RTX_TRACE_ANY, a lane parks at
 // its first accepted primitive.
+// (In rtxd itself, not in the unit's anonymous namespace: the kernel's host-side handle is then a symbol of the
+// library's dynamic table, which is how rtx_launch_name.h names a launch and tests/block_kernels.txt lists it.)
 template <bool COUNT, bool QUADS, bool FIXED, bool ANY>
 __global__ __launch_bounds__(64 * WALK_WAVES) void trace_rays(TraceParams p) {
     extern __shared__ float4 lds_entries[];
@@ -130,13 +135,16 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void trace_rays(TraceParams p) {
     }
 }
 
+namespace {
+
 template <bool COUNT, bool QUADS, bool FIXED>
 hipError_t launch_any(const TraceParams& p, hipStream_t stream) {
     const size_t shmem = FIXED ? walk_lds_bytes(p.scene.n_entries, p.scene.n_quads) : 0;
     const uint64_t waves = ((uint64_t)p.n + p.range - 1) / p.range;
     const dim3 grid((uint32_t)((waves + WALK_WAVES - 1) / WALK_WAVES)), block(64 * WALK_WAVES);
-    if (p.flags & RTX_TRACE_ANY) hipLaunchKernelGGL((trace_rays<COUNT, QUADS, FIXED, true>), grid, block, shmem, stream, p);
-    else hipLaunchKernelGGL((trace_rays<COUNT, QUADS, FIXED, false>), grid, block, shmem, stream, p);
+    const auto kern = p.flags & RTX_TRACE_ANY ? &trace_rays<COUNT, QUADS, FIXED, true> : &trace_rays<COUNT, QUADS, FIXED, false>;
+    name_launch(kern);
+    hipLaunchKernelGGL(kern, grid, block, shmem, stream, p);
     return hipGetLastError();
 }
 

@@ -1,15 +1,20 @@
 #!/bin/bash
 # Instruction-for-instruction comparison of the gfx950 kernels of two built objects (no GPU needed):
-#   bash scripts/kernel_isa_diff.sh A.o B.o
+#   bash scripts/kernel_isa_diff.sh [--demangled] A.o B.o
+# --demangled pairs the kernels by demangled name with "(anonymous namespace)::" removed instead of by symbol: for a
+# change that moves kernels between an anonymous namespace and its parent, which renames every symbol.
 # Per kernel symbol present in both, the disassemblies (llvm-objdump -d) are compared after masking what moves when
 # other code of the object comes or goes:
 #   - the trailing "// address: encoding" comments;
 #   - the numeric ids inside local labels (LBB<n>_, and the %= ids of inline-asm labels such as LP<n>_0, LG<n>);
 #   - the literal of the s_add_u32 that follows an s_getpc_b64 (a PC-relative distance to read-only data);
-#   - the alignment padding after a kernel's last instruction.
+#   - the alignment padding after a kernel's last instruction (s_nop 0, s_code_end, and the "..." llvm-objdump prints
+#     for a run of zero bytes).
 # Prints the kernels only in A, only in B, and those that differ; exit status 1 when a common kernel differs.
 set -o pipefail
-[ $# -eq 2 ] || { echo "usage: $0 A.o B.o" >&2; exit 2; }
+PAIR=symbol
+if [ "$1" = --demangled ]; then PAIR=demangled; shift; fi
+[ $# -eq 2 ] || { echo "usage: $0 [--demangled] A.o B.o" >&2; exit 2; }
 T=$(mktemp -d); trap 'rm -rf "$T"' EXIT
 L=/opt/rocm/lib/llvm/bin
 for s in a b; do
@@ -19,9 +24,9 @@ for s in a b; do
     $L/llvm-readelf -sW "$T/$s.co" | awk '$4 == "FUNC" && $7 != "UND" {print $8}' > "$T/$s.funcs" && \
     $L/llvm-objdump -d "$T/$s.co" > "$T/$s.dis" || exit 2
 done
-python3 - "$T" <<'EOF'
-import re, sys
-T = sys.argv[1]
+python3 - "$T" $PAIR <<'EOF'
+import re, subprocess, sys
+T, PAIR = sys.argv[1:3]
 HEAD = re.compile(r"^[0-9a-f]+ <(.+)>:$")
 LABEL = re.compile(r"\b(L[A-Z]+)\d+")
 LIT = re.compile(r"(s_add_u32\s+\S+,\s*\S+,\s*)\S+")
@@ -45,8 +50,13 @@ def kernels(s):
         getpc = line.startswith("s_getpc_b64")
         cur.append(line)
     for body in out.values():  # (the padding after a kernel's last instruction depends on where the next one starts)
-        while body and body[-1] in ("s_nop 0", "s_code_end"):
+        while body and body[-1] in ("s_nop 0", "s_code_end", "..."):  # ("...": llvm-objdump's run of zero bytes)
             body.pop()
+    if PAIR == "demangled":
+        names = list(out)
+        plain = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
+        out = {d.replace("(anonymous namespace)::", ""): out[n] for n, d in zip(names, plain)}
+        assert len(out) == len(names), "two kernels share a demangled name"
     return out
 
 

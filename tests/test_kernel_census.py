@@ -83,8 +83,9 @@ UNREACHABLE = {}
 
 
 # ---- the CPU test ---------------------------------------------------------------------------------------------------
-def library_kernels(path: str = LIB) -> set:
-    """The render kernels' handle symbols of the library (weak objects named as the kernels are)."""
+def library_kernels(path: str = LIB, KERNEL=KERNEL) -> set:
+    """The render kernels' handle symbols of the library (weak objects named as the kernels are); KERNEL: the pattern of
+    another set of kernels (tests/test_block_census.py)."""
     nm = shutil.which("nm")
     if nm:
         out = subprocess.run([nm, "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
@@ -506,10 +507,12 @@ RESULTS = {}  # family -> the child's report
 CHILD_TIMEOUT_S = 120
 
 
-def run_family(family: str) -> dict:
+def run_family(family: str, module: str = "test_kernel_census", STARTED=STARTED, RESULTS=RESULTS) -> dict:
+    """One child process for `family` of `module` (this one, or tests/test_block_census.py with its own STARTED and
+    RESULTS; STOPPED is shared: after a fault no child of either module starts)."""
     STARTED.append(family)
     assert not STOPPED, f"not started: {STOPPED[0]}"
-    code =("import sys; sys.path[:0] = ['raytracer-go_amd', 'tests']; import test_kernel_census as t; "
+    code =(f"import sys; sys.path[:0] = ['raytracer-go_amd', 'tests']; import {module} as t; "
             f"sys.exit(t.child_main({family!r}))")
     env = dict(os.environ, RTX_WATCHDOG_S="10", RTX_DEBUG_LAUNCH="1")
     try:
